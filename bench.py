@@ -18,6 +18,13 @@ in DESIGN.md §7, never reported as `value`.
 Contract: W untimed warmup steps, then exactly K timed steps bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX over ranks; rank 0
 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the line. `--full` adds the legs that take runs
+of their own (today: the CPU-oracle baseline, reported as `cpu_baseline`,
+null in a plain run). `--dump-outputs DIR` writes what the last timed
+step returned to its caller (see dump_outputs) for build-to-build
+comparison; inputs depend only on the arguments (seeded generator).
 """
 import argparse
 import json
@@ -44,7 +51,14 @@ def parse_args():
     p.add_argument("--warmup", type=int, default=6)
     p.add_argument("--sf", type=float, default=0.0, help="0 = auto by N")
     p.add_argument("--batch-rows", type=int, default=0, help="0 = auto")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline figure "
+                        "(the CPU-oracle baseline); off by default")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU-oracle baseline leg")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed "
+                        "step's outputs as DIR/<name>.npy (float64)")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--call-profile", action="store_true",
                    help="print per-engine-call wall time breakdown")
@@ -85,6 +99,50 @@ class CallProfiler:
         for m, (tt, calls) in sorted(self.t.items(), key=lambda x: -x[1][0]):
             print(f"#   {m:18s} {tt*1e3:9.2f} ms total  {calls:5d} calls  "
                   f"{tt*1e3/max(steps,1):7.2f} ms/step", file=sys.stderr)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _words_f64(a, n):
+    """Raw little-endian column bytes -> [n, words] float64 of their
+    uint32 words (exact: every word < 2^32)."""
+    a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    if n == 0:
+        return np.zeros((0, 0), np.float64)
+    return a.view("<u4").reshape(n, -1).astype(np.float64)
+
+
+def dump_outputs(dirname, cols, rank=0, world=1):
+    """Write one out-batch (keys, vals, times, diffs as the engine's
+    to_host() returns them; None = the step produced no output) as
+    float64 .npy files: `keys`/`vals` are the rows' raw bytes as uint32
+    words (lossless for any 64-bit content), `times`/`diffs` the values
+    themselves, `n_rows` the full row count. Above 64 MB in all a fixed
+    seeded row sample (ascending row order) is written and `sample_rows`
+    holds the chosen row indices."""
+    os.makedirs(dirname, exist_ok=True)
+    if cols is None:
+        cols = (np.empty(0, np.uint64), np.empty(0, np.uint8),
+                np.empty(0, np.uint64), np.empty(0, np.int64))
+    keys, vals, times, diffs = cols
+    n = len(times)
+    arrs = {"keys": _words_f64(keys, n), "vals": _words_f64(vals, n),
+            "times": np.asarray(times).astype(np.float64),
+            "diffs": np.asarray(diffs).astype(np.float64)}
+    # float64 per row: key + val words, time, diff, sample_rows entry;
+    # 4 KB of headroom for the .npy headers and n_rows
+    row_bytes = 8 * (arrs["keys"].shape[1] + arrs["vals"].shape[1] + 3)
+    cap = (DUMP_MAX_BYTES - 4096) // row_bytes
+    if n > cap:
+        pick = np.sort(np.random.default_rng(0).choice(n, cap,
+                                                       replace=False))
+        arrs = {k: a[pick] for k, a in arrs.items()}
+        arrs["sample_rows"] = pick.astype(np.float64)
+    arrs["n_rows"] = np.array([n], np.float64)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
 
 
 def stage_churn(churn, t, device):
@@ -328,6 +386,16 @@ def main_q17(args):
                          if args.backend != "gloo" else "cpu")
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.cpu())
+    if args.dump_outputs:
+        # step_dev applies its corrections to the maintained result, which
+        # is what the caller holds after the last timed step
+        ks = sorted(df.result)
+        sfx = "" if world == 1 else f"_rank{rank}"
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, f"result_keys{sfx}.npy"),
+                np.array(ks, np.float64))
+        np.save(os.path.join(args.dump_outputs, f"result_sums{sfx}.npy"),
+                np.array([float(df.result[k]) for k in ks], np.float64))
     probe_ms, probe_rows, probe_launches = ctx.probe_stats()
     import ctypes as C
     pairs, batches, alg_bytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -350,7 +418,7 @@ def main_q17(args):
                      "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK, "traffic": None},
         "cpu_baseline": (run_cpu_baseline_q17(args.seed, batch_rows, sf=sf)
-                         if rank == 0 and N == 1
+                         if rank == 0 and N == 1 and args.full
                          and not args.no_cpu_baseline else None),
         "probe_kernel": {"ms_total": probe_ms,
                          "launch_pairs": probe_launches // 2,
@@ -446,11 +514,18 @@ def main():
         ctx.prof_dump()  # reset engine sub-phase counters before timing
     ctx.set_kernel_timing(1)
     step_times = [] if os.environ.get("MZ_BENCH_STEP_TIMES") else None
+    # --dump-outputs keeps the last timed step's corrections alive past
+    # the window (released after the copy-out below)
+    keep = W + K - 1 if args.dump_outputs else -1
+    last_corr = None
     t0 = time.perf_counter()
     for i in range(W, W + K):
         corr = df.step_dev(staged[i], i + 1, next_upd=nxt(i))
         if corr is not None:
-            corr.release()
+            if i == keep:
+                last_corr = corr
+            else:
+                corr.release()
         if step_times is not None:
             torch.cuda.synchronize()  # not mz_gpu_sync: keep pendings
             step_times.append(time.perf_counter() - t0 -
@@ -464,6 +539,11 @@ def main():
         print("# step_ms " + " ".join(f"{s*1e3:.1f}" for s in step_times),
               file=sys.stderr)
     ctx.set_kernel_timing(0)
+    if args.dump_outputs:
+        cols = last_corr.to_host() if last_corr is not None else None
+        if last_corr is not None:
+            last_corr.release()
+        dump_outputs(args.dump_outputs, cols, rank, world)
     if prof:
         print(f"# step wall {elapsed/K*1e3:.2f} ms; breakdown:",
               file=sys.stderr)
@@ -512,7 +592,7 @@ def main():
         pass
 
     cpu_baseline = None
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if rank == 0 and N == 1 and args.full and not args.no_cpu_baseline:
         # same batch size as the GPU run (bounded step count)
         bsteps = 4 if batch_rows <= 200_000 else 2
         cpu_baseline = run_cpu_baseline(args.seed, batch=batch_rows,
