@@ -154,7 +154,12 @@ typedef struct {
 enum {
   MZ_AGG_COUNT = 0,
   MZ_AGG_SUM_I64,    /* also exact-decimal sums (i64 cents etc.)       */
-  MZ_AGG_SUM_F64     /* fixed-point accumulation, reduce.rs:1641-1697  */
+  MZ_AGG_SUM_F64,    /* fixed-point accumulation, reduce.rs:1641-1697  */
+  /* Hierarchical aggregates — mz_gpu_collation_* only (mz_gpu_reduce_create
+   * rejects them). The datum is `width` (4 or 8) bytes at `off`, signed
+   * little-endian, sign-extended to i64; `nullable` must be 0. */
+  MZ_AGG_MIN_I64,
+  MZ_AGG_MAX_I64
 };
 
 typedef struct {
@@ -440,6 +445,46 @@ mz_gpu_minmax *mz_gpu_minmax_create(mz_gpu_ctx *ctx,
 int  mz_gpu_minmax_push(mz_gpu_ctx *ctx, mz_gpu_minmax *op,
                         const mz_gpu_updates *delta, mz_gpu_out **out);
 void mz_gpu_minmax_drop(mz_gpu_ctx *ctx, mz_gpu_minmax *op);
+
+/* ------------------------------------------------------- collated reduce
+ * Replaces ReducePlan::Collation / build_collation
+ * (src/compute/src/render/reduce.rs): a GROUP BY that mixes reduction
+ * types, e.g. COUNT(*), SUM(a), MIN(b), MAX(c). Each reduction type runs on
+ * its own — one accumulable sub-reduce over all COUNT/SUM aggregates, one
+ * hierarchical bucket tree per MIN/MAX aggregate — and a final stitch
+ * keeps, per key, every part's current value and emits one output row per
+ * key in the SQL aggregate order.
+ *
+ * Output row: one 24-byte slot per aggregate in spec order. COUNT/SUM
+ * slots are the mz_gpu_reduce_* slots; a MIN/MAX slot is [0] = 0 (never
+ * null), [8..16) = the i64 extremum, remaining bytes zero.
+ * Corrections follow the reduce_abelian contract: per changed key -1 of
+ * the old stitched row and +1 of the new one, nothing when they are
+ * byte-equal, only the retraction when the group becomes empty; the output
+ * is consolidated and in canonical order.
+ *
+ * Restrictions (each an error via mz_gpu_last_error): fixed-width schemas
+ * only; single-timestamp pushes (upper <= lower + 1); 1..MZ_GPU_MAX_AGGS
+ * aggregates, each reading inside in.val_bytes; MIN/MAX inputs not
+ * nullable. A key present in some reduction types but not in others (only
+ * possible with negative input multiplicities) fails the push with
+ * "collation: key missing a reduction type" — the condition the reference
+ * logs as an error in its collation reduce. */
+typedef struct {
+  uint32_t n_aggs;                         /* 1..MZ_GPU_MAX_AGGS, SQL order  */
+  mz_gpu_aggregate aggs[MZ_GPU_MAX_AGGS];  /* any mix of the five funcs      */
+  mz_gpu_schema in;                        /* input (key,val), fixed width   */
+  mz_gpu_schema out;                       /* key_words = in.key_words,
+                                              val_bytes = 24 * n_aggs        */
+  uint32_t n_levels;                       /* minmax bucket tree, 1..4       */
+  uint32_t buckets[4];                     /* e.g. {256,16,1}; last == 1     */
+} mz_gpu_collation_spec;
+typedef struct mz_gpu_collation mz_gpu_collation;
+mz_gpu_collation *mz_gpu_collation_create(mz_gpu_ctx *ctx,
+                                          const mz_gpu_collation_spec *spec);
+int  mz_gpu_collation_push(mz_gpu_ctx *ctx, mz_gpu_collation *op,
+                           const mz_gpu_updates *delta, mz_gpu_out **out);
+void mz_gpu_collation_drop(mz_gpu_ctx *ctx, mz_gpu_collation *op);
 
 /* ------------------------------------------------------------------ peek
  * Replaces the peek path (handle_peek/process_peeks,

@@ -22,7 +22,10 @@ MZ_COMPUTE_DIV_I64 = 3
 MZ_COMPUTE_MUL_I64 = 4
 MZ_COMPUTE_CMP_FIELDS = 5
 MZ_GPU_VARLEN = 0xFFFFFFFF
-MZ_AGG_COUNT, MZ_AGG_SUM_I64, MZ_AGG_SUM_F64 = range(3)
+(MZ_AGG_COUNT, MZ_AGG_SUM_I64, MZ_AGG_SUM_F64, MZ_AGG_MIN_I64,
+ MZ_AGG_MAX_I64) = range(5)
+# hierarchical aggregates (collated reduce only)
+AGG_MIN_I64, AGG_MAX_I64 = MZ_AGG_MIN_I64, MZ_AGG_MAX_I64
 
 MZ_GPU_MAX_FILTERS = 6
 MZ_GPU_MAX_FIELDS = 8
@@ -109,6 +112,18 @@ class ReduceSpec(C.Structure):
         ("aggs", Aggregate * MZ_GPU_MAX_AGGS),
         ("in_", Schema),
         ("out", Schema),
+    ]
+
+
+class CollationSpec(C.Structure):
+    """mz_gpu_collation_spec: a GROUP BY mixing COUNT/SUM with MIN/MAX."""
+    _fields_ = [
+        ("n_aggs", C.c_uint32),
+        ("aggs", Aggregate * MZ_GPU_MAX_AGGS),
+        ("in_", Schema),
+        ("out", Schema),
+        ("n_levels", C.c_uint32),
+        ("buckets", C.c_uint32 * 4),
     ]
 
 
@@ -288,3 +303,67 @@ def reduce_spec(aggs, in_schema):
     sp.out = Schema(key_words=in_schema.key_words,
                     val_bytes=AGG_SLOT_BYTES * len(aggs))
     return sp
+
+
+def is_hierarchical(agg):
+    """MIN/MAX: maintained by the bucket tree, not by accumulation."""
+    return agg.func in (MZ_AGG_MIN_I64, MZ_AGG_MAX_I64)
+
+
+def collation_spec(aggs, in_schema, buckets=(256, 16, 1)):
+    """mz_gpu_collation_spec for `aggs` (SQL order, any mix of the five
+    funcs) over `in_schema`. Fills `out` and checks the operator's
+    restrictions here as well as in the C layer (ValueError)."""
+    aggs = list(aggs)
+    buckets = list(buckets)
+    if not 1 <= len(aggs) <= MZ_GPU_MAX_AGGS:
+        raise ValueError(
+            f"collation: n_aggs must be 1..{MZ_GPU_MAX_AGGS}, "
+            f"got {len(aggs)}")
+    if in_schema.val_bytes == MZ_GPU_VARLEN:
+        raise ValueError("collation: varlen vals unsupported")
+    if in_schema.key_words not in (1, 2):
+        raise ValueError("collation: key_words must be 1 or 2")
+    if not 1 <= len(buckets) <= 4:
+        raise ValueError("collation: 1..4 bucket levels")
+    if any(b < 1 for b in buckets) or buckets[-1] != 1:
+        raise ValueError("collation: buckets must be positive and end "
+                         "with 1")
+    for i, a in enumerate(aggs):
+        if a.func > MZ_AGG_MAX_I64:
+            raise ValueError(f"collation: aggregate {i}: unknown func "
+                             f"{a.func}")
+        if is_hierarchical(a) and a.nullable:
+            raise ValueError(f"collation: aggregate {i}: nullable MIN/MAX "
+                             "inputs unsupported")
+        if a.func == MZ_AGG_COUNT and not a.nullable:
+            continue  # COUNT(*) reads nothing
+        if a.width not in (4, 8):
+            raise ValueError(f"collation: aggregate {i}: width must be 4 "
+                             "or 8")
+        if a.off + a.width + (1 if a.nullable else 0) > in_schema.val_bytes:
+            raise ValueError(f"collation: aggregate {i} reads past "
+                             f"in.val_bytes ({in_schema.val_bytes})")
+    sp = CollationSpec()
+    sp.n_aggs = len(aggs)
+    for i, a in enumerate(aggs):
+        sp.aggs[i] = a
+    sp.in_ = in_schema
+    sp.out = Schema(key_words=in_schema.key_words,
+                    val_bytes=AGG_SLOT_BYTES * len(aggs))
+    sp.n_levels = len(buckets)
+    for i, b in enumerate(buckets):
+        sp.buckets[i] = b
+    return sp
+
+
+def collation_parts(spec):
+    """The operator's part order for `spec`: part 0 is the accumulable
+    sub-reduce (the indices of its aggregates, in their relative order;
+    absent when there are none), then one part per MIN/MAX aggregate.
+    Returns a list of index lists into spec.aggs."""
+    idx = range(spec.n_aggs)
+    acc = [i for i in idx if not is_hierarchical(spec.aggs[i])]
+    parts = [acc] if acc else []
+    parts += [[i] for i in idx if is_hierarchical(spec.aggs[i])]
+    return parts

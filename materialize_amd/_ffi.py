@@ -8,8 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (Closure, OutBatch, ReduceSpec, Schema, TopKSpec, Updates,
-                   out_to_numpy)
+from ._abi import (Closure, CollationSpec, OutBatch, ReduceSpec, Schema,
+                   TopKSpec, Updates, out_to_numpy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "csrc", "libmzgpu.so")
@@ -132,6 +132,13 @@ def load():
                                        C.POINTER(Updates),
                                        C.POINTER(C.POINTER(OutBatch))]
     lib.mz_gpu_minmax_drop.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mz_gpu_collation_create.restype = C.c_void_p
+    lib.mz_gpu_collation_create.argtypes = [C.c_void_p,
+                                            C.POINTER(CollationSpec)]
+    lib.mz_gpu_collation_push.argtypes = [C.c_void_p, C.c_void_p,
+                                          C.POINTER(Updates),
+                                          C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_collation_drop.argtypes = [C.c_void_p, C.c_void_p]
     lib.mz_gpu_join_drop.argtypes = [C.c_void_p, C.c_void_p]
     lib.mz_gpu_reduce_drop.argtypes = [C.c_void_p, C.c_void_p]
     lib.mz_gpu_peek.argtypes = [C.c_void_p, C.c_void_p,
@@ -270,7 +277,10 @@ class GpuCtx:
         return self._take(outp)
 
     def reduce_create(self, spec):
-        return self.lib.mz_gpu_reduce_create(self.ctx, C.byref(spec))
+        op = self.lib.mz_gpu_reduce_create(self.ctx, C.byref(spec))
+        if not op:
+            raise MzGpuError(self.lib.mz_gpu_last_error(self.ctx).decode())
+        return op
 
     def reduce_push(self, op, upd):
         outp = C.POINTER(OutBatch)()
@@ -348,6 +358,22 @@ class GpuCtx:
         self._check(self.lib.mz_gpu_minmax_push(self.ctx, op, C.byref(upd),
                                                 C.byref(outp)))
         return self._take(outp)
+
+    def collation_create(self, spec):
+        op = self.lib.mz_gpu_collation_create(self.ctx, C.byref(spec))
+        if not op:
+            raise MzGpuError(self.lib.mz_gpu_last_error(self.ctx).decode())
+        return op
+
+    def collation_push(self, op, upd):
+        outp = C.POINTER(OutBatch)()
+        self._check(self.lib.mz_gpu_collation_push(self.ctx, op,
+                                                   C.byref(upd),
+                                                   C.byref(outp)))
+        return self._take(outp)
+
+    def collation_drop(self, op):
+        self.lib.mz_gpu_collation_drop(self.ctx, op)
 
     def peek(self, arr, keys, time, kw=1):
         """Read (val, summed diff) per requested key as of `time`."""
@@ -448,6 +474,13 @@ class GpuCtx:
         outp = C.POINTER(OutBatch)()
         self._check(self.lib.mz_gpu_reduce_push2(
             self.ctx, op, C.byref(u1), C.byref(u2), C.byref(outp)))
+        return self._dev_out(outp, sorted=True)  # consolidated output
+
+    def collation_push_dev(self, op, upd):
+        outp = C.POINTER(OutBatch)()
+        self._check(self.lib.mz_gpu_collation_push(self.ctx, op,
+                                                   C.byref(upd),
+                                                   C.byref(outp)))
         return self._dev_out(outp, sorted=True)  # consolidated output
 
     def set_kernel_timing(self, on):

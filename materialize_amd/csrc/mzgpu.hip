@@ -111,7 +111,11 @@ __global__ void k_sortkey_val(const u8 *vals, u32 vb, u32 word,
 // per-pass min/max of all sort-key columns in one sweep (block LDS reduce
 // + one atomic per block per pass) — lets the radix passes subtract the
 // min and sort only the live bits.
-#define MAX_PASSES 12
+// One slot per sort column: time + val words + key words. 16 covers the
+// widest rows consolidated — 96-byte stitched aggregate rows (12 val
+// words) under 2-word keys; at 12 those rows' key slots aliased the max
+// half and the output came back grouped but out of canonical order.
+#define MAX_PASSES 16
 __global__ void k_pass_minmax(const u64 *keys, u32 kw, const u8 *vals,
                               u32 vb, const u64 *times, u64 n, u32 vwords,
                               int with_time, u64 *mins, u64 *maxs) {
@@ -1645,6 +1649,188 @@ __global__ void k_minmax_apply(const u64 *gkeys, u64 G, u32 kw2,
   }
 }
 
+// ------------------------------------------------------ collated reduce
+// ReducePlan::Collation / build_collation restatement (render/reduce.rs):
+// every reduction type maintains its own output ("part"); the stitch keeps
+// each key's current part values resident and emits one row per key in the
+// SQL aggregate order. Part 0 = the accumulable sub-reduce (absent when
+// the spec has no COUNT/SUM), then one part per MIN/MAX aggregate.
+//
+// Stitch state row (u64 words): [key kw][present-mask][payload], payload =
+// each part's current output val at a fixed word offset (accumulable part:
+// 3 words per slot; a MIN/MAX part: 1 word). All quantities are whole u64
+// words: part vals are 24*k or 8 bytes.
+#define COL_MAX_PARTS (MZ_GPU_MAX_AGGS + 1)
+#define COL_MAX_PW (3 * MZ_GPU_MAX_AGGS)
+struct CollateLayout {
+  u32 n_aggs, n_parts;
+  u32 W;   // tagged-stream val words (the widest part)
+  u32 PW;  // payload words
+  u32 part_off[COL_MAX_PARTS], part_len[COL_MAX_PARTS];  // payload words
+  u32 slot_src[MZ_GPU_MAX_AGGS];  // payload word offset feeding slot i
+  u32 slot_mm[MZ_GPU_MAX_AGGS];   // 1: MIN/MAX slot (one word at [8..16))
+};
+
+// MIN/MAX over a column of a wider val: the datum at `off` (4 or 8 bytes,
+// signed LE) sign-extended into the 8-byte val column the bucket tree
+// takes. Keys, times and diffs are shared with the input.
+__global__ void k_project_i64(const u8 *vals, u32 vb, u32 off, u32 width,
+                              u64 n, u8 *out) {
+  GRID_STRIDE(i, n) {
+    i64 x = d_read_int(vals + i * vb + off, (u8)width);
+    memcpy(out + i * 8, &x, 8);
+  }
+}
+
+// Append one part's correction rows to the tagged stream
+// (key, part, diff, val zero-padded to W words) at row offset `base`.
+__global__ void k_collate_pack(const u64 *pkeys, const u8 *pvals,
+                               const i64 *pdiffs, u64 m, u32 kw, u32 plen,
+                               u32 part, u32 W, u64 t, u64 base, u64 *okeys,
+                               u64 *ovals, u32 *oparts, u64 *otimes,
+                               i64 *odiffs) {
+  const u64 *pv = (const u64 *)pvals;
+  GRID_STRIDE(i, m) {
+    u64 o = base + i;
+    for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = pkeys[i * kw + w];
+    for (u32 w = 0; w < W; w++)
+      ovals[o * W + w] = w < plen ? pv[i * plen + w] : 0;
+    oparts[o] = part;
+    otimes[o] = t;
+    odiffs[o] = pdiffs[i];
+  }
+}
+
+// Stitch one key's row from its payload: accumulable slots are copied
+// from part 0, a MIN/MAX slot is its part's word in [8..16) of a zero slot.
+__device__ __forceinline__ void d_collate_stitch(const CollateLayout &L,
+                                                 const u64 *pay, u64 *row) {
+  for (u32 a = 0; a < L.n_aggs; a++) {
+    u32 s = L.slot_src[a];
+    if (L.slot_mm[a]) {
+      row[3 * a] = 0;
+      row[3 * a + 1] = pay[s];
+      row[3 * a + 2] = 0;
+    } else {
+      row[3 * a] = pay[s];
+      row[3 * a + 1] = pay[s + 1];
+      row[3 * a + 2] = pay[s + 2];
+    }
+  }
+}
+
+// Phase C of the stitch upsert (lookup / insert run as k_red_lookup /
+// k_red_insert in their own launches — RedState coherence rule): one
+// thread per changed key over the key-sorted tagged stream. `perm` maps a
+// sorted position to its tagged row; skeys are the keys gathered in
+// sorted order. Retractions apply before insertions; a key must end with
+// every part present or none (else *d_cerr is set and the key emits
+// nothing). Same uniform-iteration loop as k_reduce_apply: every lane,
+// including those past G, reaches wave_reserve. Launched with BLK threads
+// only: the bound lifts the 128-VGPR budget of the default 1024-thread
+// assumption, which spilled the two row buffers' tail to scratch.
+__global__ void __launch_bounds__(BLK) k_collate_apply(const u64 *skeys, u32 kw, const u32 *perm,
+                                const u32 *parts, const i64 *diffs,
+                                const u64 *tvals, const u32 *gstart,
+                                const u32 *gidn, u64 R, u64 t, RedState st,
+                                const u32 *found, const u32 *miss,
+                                const u32 *misspos, const u64 *d_nrows,
+                                CollateLayout L, u64 *d_cerr, u64 *okeys,
+                                u64 *ovals, u64 *otimes, i64 *odiffs,
+                                unsigned long long *ocount) {
+  u64 G = R ? gidn[R - 1] : 0;
+  u64 base = *d_nrows;
+  u32 ow = 3 * L.n_aggs;
+  u64 full = (1ull << L.n_parts) - 1;
+  u64 stride = (u64)gridDim.x * blockDim.x;
+  u64 start0 = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  u64 iters = (G + stride - 1) / stride;
+  u32 lane = threadIdx.x & 63;
+  for (u64 it = 0; it < iters; it++) {
+    u64 g = start0 + it * stride;
+    bool oe = false, ne = false;
+    const u64 *key = nullptr;
+    u64 oldrow[COL_MAX_PW], newrow[COL_MAX_PW];
+    if (g < G) {
+      u64 lo = gstart[g];
+      u64 end = (g + 1 < G) ? gstart[g + 1] : R;
+      key = skeys + lo * kw;
+      u64 idx = miss[g] ? base + misspos[g] : found[g];
+      if (idx < st.capacity) {  // overflow flagged by insert
+        u64 *row = st.rows + idx * st.stride_w;
+        u64 *pay = row + kw + 1;
+        u64 old_mask = row[kw], mask = old_mask;
+        bool bad = false;
+        if (old_mask == full) d_collate_stitch(L, pay, oldrow);
+        // retractions first: each must match the stored part payload
+        for (u64 r = lo; r < end; r++) {
+          u64 j = perm[r];
+          i64 d = diffs[j];
+          if (d == 1) continue;
+          u32 p = parts[j];
+          if (d != -1 || p >= L.n_parts || !((mask >> p) & 1)) {
+            bad = true;
+            continue;
+          }
+          const u64 *v = tvals + j * L.W;
+          bool eq = true;
+          for (u32 w = 0; w < L.part_len[p]; w++)
+            eq &= v[w] == pay[L.part_off[p] + w];
+          if (eq)
+            mask &= ~(1ull << p);
+          else
+            bad = true;
+        }
+        // then insertions: at most one per part, into a vacated part
+        for (u64 r = lo; r < end; r++) {
+          u64 j = perm[r];
+          if (diffs[j] != 1) continue;
+          u32 p = parts[j];
+          if (p >= L.n_parts || ((mask >> p) & 1)) {
+            bad = true;
+            continue;
+          }
+          const u64 *v = tvals + j * L.W;
+          for (u32 w = 0; w < L.part_len[p]; w++)
+            pay[L.part_off[p] + w] = v[w];
+          mask |= 1ull << p;
+        }
+        if (mask != 0 && mask != full) bad = true;
+        if (mask == 0)  // dead row: reclaimable by red_compact_grow
+          for (u32 w = 0; w < L.PW; w++) pay[w] = 0;
+        row[kw] = mask;
+        if (bad) {
+          *d_cerr = 1;
+        } else {
+          oe = old_mask == full;
+          ne = mask == full;
+          if (ne) d_collate_stitch(L, pay, newrow);
+          if (oe && ne) {
+            bool same = true;
+            for (u32 w = 0; w < ow; w++) same &= oldrow[w] == newrow[w];
+            if (same) oe = ne = false;
+          }
+        }
+      }
+    }
+    u32 c = (oe ? 1u : 0u) + (ne ? 1u : 0u);
+    u64 o = wave_reserve(ocount, c, lane);
+    if (oe) {
+      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
+      for (u32 w = 0; w < ow; w++) ovals[o * ow + w] = oldrow[w];
+      otimes[o] = t;
+      odiffs[o] = -1;
+      o++;
+    }
+    if (ne) {
+      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
+      for (u32 w = 0; w < ow; w++) ovals[o * ow + w] = newrow[w];
+      otimes[o] = t;
+      odiffs[o] = 1;
+    }
+  }
+}
+
 // ================================================================== host
 
 namespace {
@@ -1838,6 +2024,7 @@ struct Ctx {
   std::vector<mz_gpu_arr *> arrs;
   std::vector<mz_gpu_join *> joins;
   std::vector<mz_gpu_red *> reds;
+  std::vector<struct mz_gpu_collation *> cols;
   // pinned staging for small device->host readbacks (pageable-staged
   // async copies cost tens of microseconds each; the step does ~a dozen)
   void *pin = nullptr;
@@ -2099,6 +2286,11 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
   // the rest subtract the min and radix-sort only the live bits (end_bit)
   // -- most benchmark columns are narrow (dates, keys, small decimals).
   u32 vwords = time_major ? 0 : (vb + 7) / 8;
+  if (1 + vwords + kw > MAX_PASSES) {
+    fprintf(stderr, "sort_updates: %u sort columns exceed MAX_PASSES\n",
+            1 + vwords + kw);
+    abort();
+  }
   u64 *dminmax = (u64 *)S.get(2 * MAX_PASSES * 8);
   u64 *dmin = dminmax, *dmax = dminmax + MAX_PASSES;
   hipLaunchKernelGGL(k_init_minmax, dim3(1), dim3(BLK), 0, c->stream, dmin,
@@ -3463,6 +3655,9 @@ struct mz_gpu_ctx {
 };
 
 static void arr_flush_impl(Ctx *ctx, mz_gpu_arr *a);
+// frees a collation's stitch state and minmax parts (its accumulable
+// sub-reduce lives in ctx->reds); defined with the operator
+static void collation_free(mz_gpu_ctx *c, mz_gpu_collation *op);
 
 extern "C" {
 
@@ -3592,6 +3787,8 @@ void mz_gpu_fini(mz_gpu_ctx *c) {
     delete r;
   }
   ctx->reds.clear();
+  for (mz_gpu_collation *co : ctx->cols) collation_free(c, co);
+  ctx->cols.clear();
   for (mz_gpu_join *j : ctx->joins) delete j;
   ctx->joins.clear();
   (void)hipStreamSynchronize(ctx->stream);
@@ -4604,6 +4801,17 @@ mz_gpu_red *mz_gpu_reduce_create(mz_gpu_ctx *c,
     ctx->err = "varlen vals unsupported in reduce";
     return nullptr;
   }
+  if (spec->n_aggs > MZ_GPU_MAX_AGGS) {
+    ctx->err = "reduce: n_aggs out of range";
+    return nullptr;
+  }
+  for (u32 a = 0; a < spec->n_aggs; a++)
+    if (spec->aggs[a].func > MZ_AGG_SUM_F64) {
+      // k_reduce_apply's last branch would silently treat it as SUM_F64
+      ctx->err = "reduce: accumulable aggregates only (COUNT/SUM); MIN/MAX "
+                 "go through mz_gpu_collation_create";
+      return nullptr;
+    }
   mz_gpu_red *r = new mz_gpu_red();
   r->spec = *spec;
   u32 kw = spec->in.key_words;
@@ -5516,6 +5724,12 @@ mz_gpu_minmax *mz_gpu_minmax_create(mz_gpu_ctx *c, const mz_gpu_schema *in,
   return op;
 }
 
+// Internal: minmax over already-staged device updates at time t. Does not
+// reset the scratch arena (the public entry does) so a caller can keep its
+// own staged columns alive across several sub-pushes.
+static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
+                                u64 t, mz_gpu_out **out);
+
 int mz_gpu_minmax_push(mz_gpu_ctx *c, mz_gpu_minmax *op,
                        const mz_gpu_updates *u, mz_gpu_out **out) {
   Ctx *ctx = &c->impl;
@@ -5524,11 +5738,15 @@ int mz_gpu_minmax_push(mz_gpu_ctx *c, mz_gpu_minmax *op,
     return -1;
   }
   (*ctx->scr).reset();
+  DevUpdates d0 = stage_updates(ctx, u, op->kw, 8);
+  return minmax_push_dev_impl(ctx, op, d0, u->lower, out);
+}
+
+static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
+                                u64 t, mz_gpu_out **out) {
   auto &S = (*ctx->scr);
-  u64 t = u->lower;
   u32 kw = op->kw, kw2 = kw + 1;
   u32 L = (u32)op->buckets.size();
-  DevUpdates d0 = stage_updates(ctx, u, kw, 8);
   // level-0 input keys: (key, b0(val))
   u64 n = d0.n;
   u64 *bkeys = (u64 *)S.get(std::max<u64>(n, 1) * kw2 * 8);
@@ -5636,6 +5854,308 @@ void mz_gpu_minmax_drop(mz_gpu_ctx *c, mz_gpu_minmax *op) {
     dfree(ctx, st.rows);
   }
   delete op;
+}
+
+// ------------------------------------------------------ collated reduce op
+struct mz_gpu_collation {
+  mz_gpu_collation_spec spec;
+  CollateLayout L;
+  mz_gpu_red *red = nullptr;        // part 0 (null: no accumulable aggs)
+  std::vector<mz_gpu_minmax *> mms;  // one part per MIN/MAX aggregate
+  std::vector<mz_gpu_aggregate> mm_aggs;
+  RedState st;                      // resident stitch state
+  u64 n_rows = 0;                   // host mirror of *d_nrows
+  u64 *d_nrows = nullptr;
+  u64 *d_err = nullptr;             // [0] capacity, [1] missing part
+  // The parts run on this arena: the main arena holds the staged input
+  // and the projected columns across all parts and is reset once per
+  // push, while a part may reset its arena freely (a bucket level's spine
+  // merge does).
+  Scratch sub;
+};
+
+namespace {
+struct ScrGuard {
+  Ctx *c;
+  Scratch *prev;
+  ScrGuard(Ctx *ctx, Scratch *s) : c(ctx), prev(ctx->scr) {
+    s->reset();
+    c->scr = s;
+  }
+  ~ScrGuard() { c->scr = prev; }
+};
+}  // namespace
+
+static void collation_free(mz_gpu_ctx *c, mz_gpu_collation *op) {
+  Ctx *ctx = &c->impl;
+  for (mz_gpu_minmax *m : op->mms) mz_gpu_minmax_drop(c, m);
+  for (void *p : {(void *)op->st.hash, (void *)op->st.rows,
+                  (void *)op->d_nrows, (void *)op->d_err})
+    dfree(ctx, p);
+  (void)hipStreamSynchronize(ctx->stream);
+  op->sub.destroy();
+  delete op;
+}
+
+mz_gpu_collation *mz_gpu_collation_create(mz_gpu_ctx *c,
+                                          const mz_gpu_collation_spec *spec) {
+  Ctx *ctx = &c->impl;
+  auto fail = [&](const char *msg) -> mz_gpu_collation * {
+    ctx->err = msg;
+    return nullptr;
+  };
+  if (is_varlen(spec->in.val_bytes) || is_varlen(spec->out.val_bytes))
+    return fail("collation: varlen vals unsupported");
+  if (spec->n_aggs < 1 || spec->n_aggs > MZ_GPU_MAX_AGGS)
+    return fail("collation: n_aggs out of range");
+  u32 kw = spec->in.key_words;
+  if (kw < 1 || kw > 2) return fail("collation: key_words must be 1 or 2");
+  if (spec->out.key_words != kw || spec->out.val_bytes != 24 * spec->n_aggs)
+    return fail("collation: out schema must be (in.key_words, 24 * n_aggs)");
+  if (spec->n_levels < 1 || spec->n_levels > 4)
+    return fail("collation: n_levels out of range");
+  for (u32 l = 0; l < spec->n_levels; l++)
+    if (spec->buckets[l] == 0 ||
+        (l + 1 == spec->n_levels && spec->buckets[l] != 1))
+      return fail("collation: buckets must be non-zero and end with 1");
+  u32 n_acc = 0, n_mm = 0;
+  for (u32 a = 0; a < spec->n_aggs; a++) {
+    const mz_gpu_aggregate &g = spec->aggs[a];
+    if (g.func > MZ_AGG_MAX_I64) return fail("collation: unknown aggregate");
+    bool mm = g.func >= MZ_AGG_MIN_I64;
+    if (mm && g.nullable)
+      return fail("collation: nullable MIN/MAX inputs unsupported");
+    if (g.func != MZ_AGG_COUNT || g.nullable) {  // COUNT(*) reads nothing
+      if (g.width != 4 && g.width != 8)
+        return fail("collation: aggregate width must be 4 or 8");
+      if ((u64)g.off + g.width + (g.nullable ? 1 : 0) > spec->in.val_bytes)
+        return fail("collation: aggregate reads past in.val_bytes");
+    }
+    (mm ? n_mm : n_acc)++;
+  }
+  auto *op = new mz_gpu_collation();
+  op->spec = *spec;
+  // layout: part 0 = accumulable (if any), then the MIN/MAX parts in order
+  CollateLayout &L = op->L;
+  memset(&L, 0, sizeof(L));
+  L.n_aggs = spec->n_aggs;
+  u32 part = 0, off = 0;
+  mz_gpu_reduce_spec rs{};
+  if (n_acc) {
+    L.part_off[0] = 0;
+    L.part_len[0] = 3 * n_acc;
+    off = 3 * n_acc;
+    part = 1;
+  }
+  u32 acc_rank = 0;
+  for (u32 a = 0; a < spec->n_aggs; a++) {
+    const mz_gpu_aggregate &g = spec->aggs[a];
+    if (g.func >= MZ_AGG_MIN_I64) {
+      L.part_off[part] = off;
+      L.part_len[part] = 1;
+      L.slot_src[a] = off;
+      L.slot_mm[a] = 1;
+      off++;
+      part++;
+      op->mm_aggs.push_back(g);
+    } else {
+      L.slot_src[a] = 3 * acc_rank;
+      L.slot_mm[a] = 0;
+      rs.aggs[acc_rank++] = g;
+    }
+  }
+  L.n_parts = part;
+  L.PW = off;
+  L.W = n_acc ? 3 * n_acc : 1;
+  if (n_acc) {
+    rs.n_aggs = n_acc;
+    rs.in = spec->in;
+    rs.out = {kw, 24 * n_acc};
+    op->red = mz_gpu_reduce_create(c, &rs);
+    if (!op->red) {
+      delete op;
+      return nullptr;
+    }
+  }
+  mz_gpu_schema mm_in{kw, 8};
+  for (u32 j = 0; j < n_mm; j++)
+    op->mms.push_back(mz_gpu_minmax_create(
+        c, &mm_in, op->mm_aggs[j].func == MZ_AGG_MAX_I64, spec->buckets,
+        spec->n_levels));
+  u64 cap = 1ull << 20;  // grows on demand; env override for tests/tuning
+  if (const char *e = getenv("MZ_GPU_COL_CAP")) cap = (u64)atoll(e);
+  u64 p2 = 16;  // the hash masks with slots - 1: keep a power of two
+  while (p2 < cap) p2 *= 2;
+  cap = p2;
+  RedState &st = op->st;
+  st.slots = 2 * cap;
+  st.capacity = cap;
+  st.stride_w = kw + 1 + L.PW;
+  st.hash = dnew<u64>(ctx, st.slots * (kw + 1));
+  st.rows = dnew<u64>(ctx, cap * st.stride_w);
+  op->d_nrows = dnew<u64>(ctx, 1);
+  op->d_err = dnew<u64>(ctx, 2);
+  fill_u64(ctx, op->d_nrows, 1, 0);
+  fill_u64(ctx, op->d_err, 2, 0);
+  fill_u64(ctx, st.hash, st.slots * (kw + 1), ~0ull);
+  ctx->cols.push_back(op);
+  return op;
+}
+
+void mz_gpu_collation_drop(mz_gpu_ctx *c, mz_gpu_collation *op) {
+  Ctx *ctx = &c->impl;
+  if (op->red) mz_gpu_reduce_drop(c, op->red);
+  auto &v = ctx->cols;
+  v.erase(std::remove(v.begin(), v.end(), op), v.end());
+  collation_free(c, op);
+}
+
+int mz_gpu_collation_push(mz_gpu_ctx *c, mz_gpu_collation *op,
+                          const mz_gpu_updates *u, mz_gpu_out **out) {
+  Ctx *ctx = &c->impl;
+  if (u->upper > u->lower + 1) {
+    ctx->err = "collation_push: single-timestamp batches only";
+    return -1;
+  }
+  MZ_PROF(ctx, "collation_push");
+  // the ONE reset of the main arena: the staged input and the projected
+  // columns below must survive every part's push
+  (*ctx->scr).reset();
+  auto &S = (*ctx->scr);
+  const CollateLayout &L = op->L;
+  u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
+  u32 ovb = op->spec.out.val_bytes;
+  u64 t = u->lower;
+  DevUpdates d = stage_updates(ctx, u, kw, vb);
+  u64 n = d.n;
+  auto empty_out = [&]() {
+    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
+                    dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, kw, ovb);
+    return 0;
+  };
+  if (n == 0) return empty_out();
+  // ---- parts: each reduction type on its own, over the same input
+  std::vector<mz_gpu_out *> pouts(L.n_parts, nullptr);
+  auto release_parts = [&]() {
+    for (mz_gpu_out *o : pouts)
+      if (o) mz_gpu_out_release(c, o);
+  };
+  u32 part = 0;
+  if (op->red) {
+    MZ_PROF(ctx, "collation_accumulable");
+    ScrGuard sg(ctx, &op->sub);
+    if (reduce_push_dev_impl(ctx, op->red, d, u->lower, u->upper,
+                             &pouts[0]) != 0)
+      return -1;
+    part = 1;
+  }
+  for (size_t j = 0; j < op->mms.size(); j++, part++) {
+    MZ_PROF(ctx, "collation_minmax");
+    const mz_gpu_aggregate &g = op->mm_aggs[j];
+    u8 *pv = (u8 *)S.get(n * 8);
+    hipLaunchKernelGGL(k_project_i64, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, d.vals, vb, (u32)g.off, (u32)g.width, n,
+                       pv);
+    DevUpdates dp{d.keys, pv, d.times, d.diffs, n};
+    ScrGuard sg(ctx, &op->sub);
+    if (minmax_push_dev_impl(ctx, op->mms[j], dp, t, &pouts[part]) != 0) {
+      release_parts();
+      return -1;
+    }
+  }
+  u64 R = 0;
+  for (mz_gpu_out *o : pouts) R += o->n;
+  if (R == 0) {
+    release_parts();
+    return empty_out();
+  }
+  MZ_PROF(ctx, "collation_stitch");
+  // every changed key has a correction row in some part, and an input row
+  if (op->n_rows + std::min(R, n) > op->st.capacity)
+    red_compact_grow(ctx, op->st, op->d_nrows, op->n_rows, std::min(R, n),
+                     kw, kw);
+  // ---- tagged stream (key, part, diff, val padded), sorted by key
+  u64 *tk = (u64 *)S.get(R * kw * 8);
+  u64 *tv = (u64 *)S.get(R * L.W * 8);
+  u32 *tp = (u32 *)S.get(R * 4);
+  u64 *tt = (u64 *)S.get(R * 8);
+  i64 *td = (i64 *)S.get(R * 8);
+  u64 base = 0;
+  for (u32 p = 0; p < L.n_parts; p++) {
+    mz_gpu_out *o = pouts[p];
+    if (o->n)
+      hipLaunchKernelGGL(k_collate_pack, dim3(ngrid(o->n)), dim3(BLK), 0,
+                         ctx->stream, o->keys, o->vals, o->diffs, o->n, kw,
+                         L.part_len[p], p, L.W, t, base, tk, tv, tp, tt, td);
+    base += o->n;
+  }
+  u32 *perm = (u32 *)S.get(R * 4);
+  sort_updates(ctx, tk, kw, nullptr, 0, tt, R, perm, false);
+  u64 *sk = (u64 *)S.get(R * kw * 8);
+  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(R)), dim3(BLK), 0,
+                     ctx->stream, tk, kw, perm, sk, R);
+  u32 *flags = (u32 *)S.get(R * 4);
+  u32 *gid = (u32 *)S.get(R * 4);
+  u32 *starts = (u32 *)S.get(R * 4);
+  hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(R)), dim3(BLK), 0,
+                     ctx->stream, sk, kw, tt, flags, R);
+  inclusive_scan_u32(ctx, flags, gid, R);
+  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(R)), dim3(BLK), 0,
+                     ctx->stream, flags, gid, starts, R);
+  // ---- stitch upsert: lookup, insert, apply as three launches
+  u32 *found = (u32 *)S.get(R * 4);
+  u32 *miss = (u32 *)S.get(R * 4);
+  u32 *misspos = (u32 *)S.get((R + 1) * 4);
+  hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(R)), dim3(BLK), 0, ctx->stream,
+                     sk, kw, starts, 0, gid, R, op->st, found, miss);
+  exclusive_scan_u32_ns(ctx, miss, misspos, R);
+  hipLaunchKernelGGL(k_red_insert, dim3(ngrid(R)), dim3(BLK), 0, ctx->stream,
+                     sk, kw, starts, 0, gid, R, miss, misspos, 0,
+                     op->d_nrows, op->d_err, op->st);
+  u64 cap_out = 2 * R + 16;  // at most two rows per changed key
+  u64 *pk = dnew<u64>(ctx, cap_out * kw);
+  u8 *pvv = (u8 *)dmalloc(ctx, cap_out * ovb);
+  u64 *pt = dnew<u64>(ctx, cap_out);
+  i64 *pd = dnew<i64>(ctx, cap_out);
+  unsigned long long *ocount = (unsigned long long *)S.get(8);
+  fill_u64(ctx, (u64 *)ocount, 1, 0);
+  hipLaunchKernelGGL(k_collate_apply, dim3(ngrid(R)), dim3(BLK), 0,
+                     ctx->stream, sk, kw, perm, tp, td, tv, starts, gid, R, t,
+                     op->st, found, miss, misspos, op->d_nrows, L,
+                     op->d_err + 1, pk, (u64 *)pvv, pt, pd, ocount);
+  hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
+                     op->d_nrows, misspos, gid, R);
+  // the stitch's one readback: count, both error words, table rows
+  u64 *stage = (u64 *)ctx->pin;
+  HIP_CHECK(hipMemcpyAsync(stage, ocount, 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(stage + 1, op->d_err, 16, hipMemcpyDeviceToHost,
+                           ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(stage + 3, op->d_nrows, 8, hipMemcpyDeviceToHost,
+                           ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  u64 emitted = stage[0], cap_err = stage[1], part_err = stage[2];
+  op->n_rows = stage[3];
+  release_parts();
+  if (cap_err || part_err) {
+    for (void *p : {(void *)pk, (void *)pvv, (void *)pt, (void *)pd})
+      dfree(ctx, p);
+    fill_u64(ctx, op->d_err, 2, 0);
+    ctx->err = cap_err ? "collation state capacity exceeded"
+                       : "collation: key missing a reduction type";
+    return -1;
+  }
+  DevUpdates pin{pk, pvv, pt, pd, emitted};
+  u64 *ok;
+  u8 *ov;
+  u64 *ot;
+  i64 *od;
+  u64 Mc;
+  consolidate_dev(ctx, kw, ovb, pin, &ok, &ov, &ot, &od, &Mc);
+  for (void *p : {(void *)pk, (void *)pvv, (void *)pt, (void *)pd})
+    dfree(ctx, p);
+  *out = make_out(ok, ov, ot, od, Mc, kw, ovb);
+  return 0;
 }
 
 // ---- numeric debug probes (test support; not part of the drop-in surface)

@@ -383,6 +383,44 @@ class ReduceOp:
         return self.ctx.reduce_push_dev(self.op, updates)
 
 
+@dataclass
+class CollationPlan:
+    """ReducePlan::Collation surface (plan/reduce.rs; rendered by
+    build_collation, reduce.rs): aggregates of more than one reduction
+    type — or a lone hierarchical one — stitched into one row per key."""
+    spec: abi.CollationSpec
+
+
+class CollationOp:
+    """build_collation: the accumulable sub-reduce and one bucket tree per
+    MIN/MAX run on their own; the resident stitch emits one output row per
+    key in the SQL aggregate order. Single-timestamp pushes only."""
+
+    def __init__(self, ctx, plan: CollationPlan):
+        self.ctx = ctx
+        self.op = ctx.collation_create(plan.spec)
+
+    def push(self, updates) -> DevOut:
+        return self.ctx.collation_push_dev(self.op, updates)
+
+    def drop(self):
+        if self.op is not None:
+            self.ctx.collation_drop(self.op)
+            self.op = None
+
+
+def plan_reduce(aggs, in_schema, **kw):
+    """Pick the reduce plan for `aggs` the way the reference does
+    (ReducePlan::create_from, plan/reduce.rs): Collation only when more
+    than one reduction type is present or the single type is hierarchical;
+    all-accumulable aggregates keep the plain ReducePlan. `kw` goes to
+    abi.collation_spec (e.g. buckets=...)."""
+    aggs = list(aggs)
+    if any(abi.is_hierarchical(a) for a in aggs):
+        return CollationPlan(abi.collation_spec(aggs, in_schema, **kw))
+    return ReducePlan(abi.reduce_spec(aggs, in_schema))
+
+
 class TopKPlan:
     """render_topk / BasicTopKPlan surface (top_k.rs:289-311,
     plan/top_k.rs): group key = the arrangement key; order columns over
@@ -432,7 +470,10 @@ def render_delta_join(ctx, arrangements, plan, exchange=None) -> DeltaJoinOp:
     return DeltaJoinOp(ctx, arrangements, plan, exchange=exchange)
 
 
-def render_reduce(ctx, plan) -> ReduceOp:
+def render_reduce(ctx, plan):
+    """ReduceOp for a ReducePlan, CollationOp for a CollationPlan."""
+    if isinstance(plan, CollationPlan):
+        return CollationOp(ctx, plan)
     return ReduceOp(ctx, plan)
 
 
