@@ -290,10 +290,21 @@ class LinearJoinOp:
     a LinearJoinPlan over the engine. Each stage is the two-sided
     mz_join_core between the stream's arrangement and the lookup
     arrangement; `step` drives one timestamp's deltas through the
-    drain-input-1-first discipline (mz_join_core.rs:237-368):
-    the stream delta probes the lookup BEFORE the lookup's delta is
-    installed, then the lookup delta probes the updated stream side —
-    each concurrent pair counted exactly once."""
+    drain discipline of mz_join_core (mz_join_core.rs:237-368):
+    of a stage's two concurrent deltas, the first one drained probes the
+    other side WITHOUT that side's delta and the second probes the other
+    side WITH it — each concurrent pair counted exactly once.
+
+    A probe sees whatever is installed at the time of the call, so the op
+    owns the drain points. Which side drains first follows from what the
+    caller has already installed: a delta that is already in its
+    arrangement is visible to every probe from the other side, so it
+    must drain FIRST — it probes the other side before that side's delta
+    goes in, and the op installs the other delta afterwards. Interior
+    stream arrangements are op-owned and never pre-installed, so interior
+    stages honour either state of the lookup. At stage 0 a pre-installed
+    source delta together with a pre-installed lookup delta cannot be
+    counted exactly once and is rejected."""
 
     def __init__(self, ctx, arrangements, plan: LinearJoinPlan):
         self.ctx = ctx
@@ -317,16 +328,33 @@ class LinearJoinOp:
         u = abi.make_updates(k, v, tm, d, t, t + 1)
         return self.ctx.map(abi.schema(in_kw, in_vb), u, cl)
 
-    def step(self, t, source_cols, lookup_deltas=None):
+    def step(self, t, source_cols, lookup_deltas=None,
+             source_installed=True):
         """One timestamp: `source_cols` = (keys, vals, times, diffs) of
-        the source relation's delta (the caller has ALREADY installed it
-        in the source arrangement — it is shared state, like the
-        reference's CollectionBundle arrangements); `lookup_deltas` maps
-        lookup relation name -> (updates_desc, already_installed: bool).
-        The op installs not-yet-installed lookup deltas at the correct
-        drain point. Returns the final output columns (host)."""
+        the source relation's delta; `source_installed` says whether the
+        caller has ALREADY installed it in the source arrangement (shared
+        state, like the reference's CollectionBundle arrangements). When
+        it has not, the op installs it — as stage 0's stream, i.e. after
+        the initial closure and stage 0's key prep — at the correct drain
+        point. `lookup_deltas` maps lookup relation name ->
+        (updates_desc, already_installed: bool); the op installs
+        not-yet-installed lookup deltas at the correct drain point too
+        (once, also when several stages probe the same relation).
+
+        Per stage, with stream delta dS and lookup delta dL:
+          lookup not installed: install dS (unless the caller did), dS
+            probes the lookup WITHOUT dL, install dL, dL probes the
+            stream WITH dS;
+          lookup installed: dL probes the stream WITHOUT dS, install dS,
+            dS probes the lookup WITH dL.
+        A pre-installed source delta cannot meet a pre-installed stage-0
+        lookup delta exactly once (both probes would see the other
+        delta): that combination raises ValueError unless one of the two
+        deltas is empty. Returns the final output columns (host); each
+        stage's output is the stream-side probe's rows followed by the
+        lookup-side probe's, not consolidated across the two."""
         ctx = self.ctx
-        lookup_deltas = lookup_deltas or {}
+        lookup_deltas = dict(lookup_deltas or {})
         plan = self.plan
         cur = source_cols
         if plan.initial_closure is not None:
@@ -339,16 +367,35 @@ class LinearJoinOp:
                                 st.stream_val_bytes)
             u = abi.make_updates(cur[0], cur[1], cur[2], cur[3], t, t + 1)
             if i > 0:
-                # interior stage: arrange the accumulated stream
-                ctx.arr_insert(self.stage_arrs[i - 1], u)
-            out1 = ctx.join_push(self.joins[i], 1, u)  # probes lookup OLD
+                # interior stage: the op arranges the accumulated stream
+                stream_arr, stream_done = self.stage_arrs[i - 1], False
+            else:
+                stream_arr = self.arrangements[plan.source_relation]
+                stream_done = source_installed
             ld = lookup_deltas.get(st.lookup_relation)
-            if ld is not None:
-                lu, installed = ld
-                if not installed:
-                    ctx.arr_insert(self.arrangements[st.lookup_relation],
-                                   lu)
-                out2 = ctx.join_push(self.joins[i], 2, lu)  # probes NEW
+            lu, installed = ld if ld is not None else (None, False)
+            if installed and stream_done and int(u.n) and int(lu.n):
+                raise ValueError(
+                    f"LinearJoinOp.step: the deltas of "
+                    f"{plan.source_relation!r} and {st.lookup_relation!r} "
+                    f"are both already installed; their concurrent pairs "
+                    f"cannot be counted exactly once (pass "
+                    f"source_installed=False and let the op install the "
+                    f"source delta)")
+            out2 = None
+            if installed:
+                # lookup delta drains first: probes the stream WITHOUT dS
+                out2 = ctx.join_push(self.joins[i], 2, lu)
+            if not stream_done:
+                ctx.arr_insert(stream_arr, u)
+            # without dL when the lookup is not installed yet, with it
+            # when it drained above
+            out1 = ctx.join_push(self.joins[i], 1, u)
+            if ld is not None and not installed:
+                ctx.arr_insert(self.arrangements[st.lookup_relation], lu)
+                lookup_deltas[st.lookup_relation] = (lu, True)
+                out2 = ctx.join_push(self.joins[i], 2, lu)  # WITH dS
+            if out2 is not None:
                 cur = tuple(np.concatenate([a, b])
                             for a, b in zip(out1, out2))
             else:

@@ -526,39 +526,37 @@ class Q17Dataflow:
                 np.full(len(k), t, np.uint64),
                 np.ascontiguousarray(d, np.int64), t, t + 1)
 
-        def seal(out_cols, vb):
-            k, v, tm, d = out_cols
-            return abi.make_updates(k, v, tm, d, t, t + 1)
-
         lp_u = updates(lp_k, lp_v, lp_d, 16)
         p_u = updates(p_k, p_v, p_d, 16)
         times = np.full(len(lp_k), t, np.uint64)
         lp_cols = (np.ascontiguousarray(lp_k, np.int64),
                    np.ascontiguousarray(lp_v, np.uint8).reshape(-1),
                    times, np.ascontiguousarray(lp_d, np.int64))
+        # Each join's op owns both installs, so it drains at the right
+        # points (render.LinearJoinOp.step; same order as step_dev).
         # --- join1 through its LinearJoinPlan: source = lineitem delta
-        # (installed first), part's delta drained as the lookup side
-        ctx.arr_insert(self.arr_l0, lp_u)
-        l1_cols = self.j1op.step(t, lp_cols, {"part": (p_u, False)})
-        l1_u = seal(l1_cols, 16)
+        # (installed by the op, probes part without part's delta), then
+        # part's delta drained as the lookup side
+        l1_cols = self.j1op.step(t, lp_cols, {"part": (p_u, False)},
+                                 source_installed=False)
         # --- distinct of l1's partkeys
         dk, dv, dt_, dd = l1_cols
         dist_u = abi.make_updates(dk, None, dt_, dd, t, t + 1)
         dcorr = ctx.reduce_push(self.distinct, dist_u)
-        dcorr_u = abi.make_updates(*dcorr, t, t + 1)
         # --- join2 through its plan: source = distinct corrections,
-        # lineitem's delta drained as the lookup side (already installed
-        # by join1's phase; the op pairs probes for exactly-once)
-        ctx.arr_insert(self.arr_dist, dcorr_u)
-        q_cols = self.j2op.step(t, dcorr, {"lineitem_by_pk": (lp_u, True)})
+        # lineitem's delta is the lookup side and already installed by
+        # join1's phase, so it drains FIRST: it probes distinct before
+        # the op installs the corrections, which then probe lineitem
+        q_cols = self.j2op.step(t, dcorr, {"lineitem_by_pk": (lp_u, True)},
+                                source_installed=False)
         # --- per-partkey sum(quantity)/count
         q_u = abi.make_updates(*q_cols, t, t + 1)
         acorr = ctx.reduce_push(self.avg, q_u)
         acorr_u = abi.make_updates(*acorr, t, t + 1)
         # --- join3 through its plan: source = l1 delta, avg corrections
         # drained as the lookup side
-        ctx.arr_insert(self.arr_l1, l1_u)
-        e_cols = self.j3op.step(t, l1_cols, {"avg": (acorr_u, False)})
+        e_cols = self.j3op.step(t, l1_cols, {"avg": (acorr_u, False)},
+                                source_installed=False)
         e_cols = self._route_total(list(e_cols))
         e_u = abi.make_updates(*e_cols, t, t + 1)
         tcorr = ctx.reduce_push(self.total, e_u)

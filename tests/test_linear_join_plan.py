@@ -2,7 +2,17 @@
 linear_join.rs:27-76; executor = render.LinearJoinOp): a 2-stage chain
 join A ⋈ B ⋈ C driven by one plan, with interior JoinStage
 arrangements, checked against a naive recompute on the oracle and
-bit-exactly GPU-vs-oracle."""
+bit-exactly GPU-vs-oracle.
+
+The concurrent-delta cases drive `op.step` over several timestamps with
+deltas on the source AND the lookup relations in the same step, for every
+combination of already-installed / not-yet-installed lookup deltas, and
+hold the output to exactly-once: per step the consolidated output equals
+naive(contents after) - naive(contents before), and accumulated over all
+steps it equals naive(final contents)."""
+import functools
+from collections import Counter
+
 import numpy as np
 import pytest
 
@@ -13,7 +23,7 @@ from materialize_amd.render import (LinearJoinPlan, LinearStagePlan,
 F = abi.field
 
 
-def _plan():
+def _plan(stages=2):
     # A arranged by k2, val=[a i64] (the source_key arrangement matches
     # stage 1's stream key, as the reference requires); B(k2) val=[k3];
     # C(k3) val=[c]
@@ -27,6 +37,7 @@ def _plan():
         [], [F(abi.MZ_SRC_KEY, 0, 8)],
         [F(abi.MZ_SRC_VAL_STREAM, 0, 8), F(abi.MZ_SRC_VAL_LOOKUP, 0, 8)],
         abi.schema(1, 16))
+    # stages=1 is the single stage A ⋈ B: the chain's first stage alone
     return LinearJoinPlan(
         source_relation="A",
         stage_plans=[
@@ -34,7 +45,7 @@ def _plan():
                             stream_val_bytes=8),
             LinearStagePlan("C", cl2, stream_key_words=1,
                             stream_val_bytes=8),
-        ])
+        ][:stages])
 
 
 def _mk(rng, n, lo, hi, extra):
@@ -43,22 +54,35 @@ def _mk(rng, n, lo, hi, extra):
     return keys, v0
 
 
-def _naive(A, B, C):
-    """dict-based recompute of the chain join result multiset."""
-    from collections import Counter
+def _rows(R):
+    """(keys, vals[, diffs]) columns -> (key, val, multiplicity) rows;
+    without a diffs column every row counts once."""
+    diffs = R[2] if len(R) > 2 else [1] * len(R[0])
+    return [(int(k), int(v), int(d)) for k, v, d in zip(R[0], R[1], diffs)]
+
+
+def _naive(A, B, C=None):
+    """dict-based recompute of the join result multiset from the current
+    contents of the relations, each given as (keys, vals[, diffs])
+    columns; a row's multiplicity is the sum of its diffs and an output
+    row's is the product of its inputs'. With C the chain A ⋈ B ⋈ C ->
+    {(k3, a, c): m}; without it the single stage A ⋈ B -> {(k3, a): m}.
+    Rows of multiplicity 0 are dropped."""
     bmap = {}
-    for k2, k3 in zip(*B):
-        bmap.setdefault(int(k2), []).append(int(k3))
+    for k2, k3, m in _rows(B):
+        bmap.setdefault(k2, []).append((k3, m))
     cmap = {}
-    for k3, c in zip(*C):
-        cmap.setdefault(int(k3), []).append(int(c))
+    for k3, c, m in _rows(C) if C is not None else ():
+        cmap.setdefault(k3, []).append((c, m))
     out = Counter()
-    ak2, aa = A
-    for k2, a in zip(ak2, aa):
-        for k3 in bmap.get(int(k2), []):
-            for c in cmap.get(int(k3), []):
-                out[(int(k3), int(a), int(c))] += 1
-    return out
+    for k2, a, ma in _rows(A):
+        for k3, mb in bmap.get(k2, ()):
+            if C is None:
+                out[(k3, a)] += ma * mb
+                continue
+            for c, mc in cmap.get(k3, ()):
+                out[(k3, a, c)] += ma * mb * mc
+    return Counter({r: m for r, m in out.items() if m})
 
 
 def _run(ctx, seed=5):
@@ -118,3 +142,279 @@ def test_two_stage_plan_gpu_matches_oracle():
                                       err_msg=what)
     g.close()
     o.close()
+
+
+# ------------------------------------------------- concurrent deltas
+#
+# Relations are multisets {(key, val): multiplicity}: A = (k2, a),
+# B = (k2, k3), C = (k3, c). A step's delta is a list of (key, val, diff)
+# rows per relation, all at the step's timestamp.
+
+RELS = ("A", "B", "C")
+COLS = ("keys", "vals", "times", "diffs")
+
+
+def _gen_delta(rng, contents, nkeys, nvals, max_rows, full=False):
+    """One relation's delta for one step, at most `max_rows` rows (exactly
+    that many with `full`): retractions of rows that exist, by no more
+    than their multiplicity, and inserts with multiplicity 1..3 whose
+    keys and vals come from ranges small enough to collide."""
+    live = sorted(contents)
+    cap = max_rows // 2
+    n_ret = min(len(live), cap if full else int(rng.integers(0, cap + 1)))
+    rows = []
+    if n_ret:
+        for i in rng.choice(len(live), n_ret, replace=False):
+            row = live[int(i)]
+            rows.append(row + (-int(rng.integers(1, contents[row] + 1)),))
+    n_ins = (max_rows - n_ret if full
+             else int(rng.integers(1, max_rows - n_ret + 1)))
+    for _ in range(n_ins):
+        rows.append((int(rng.integers(nkeys)), int(rng.integers(nvals)),
+                     int(rng.integers(1, 4))))
+    return rows
+
+
+def _contents_cols(cnt):
+    rows = sorted(cnt.items())
+    return ([r[0][0] for r in rows], [r[0][1] for r in rows],
+            [r[1] for r in rows])
+
+
+def _naive_of(contents, stages):
+    return _naive(*(_contents_cols(contents[r]) for r in RELS[:stages + 1]))
+
+
+def _minus(after, before):
+    d = Counter(after)
+    d.subtract(before)
+    return {r: m for r, m in d.items() if m}
+
+
+def _check_inputs(steps, stages):
+    """The scenario must have what the cases are about; a seed that does
+    not is a bad seed, not a pass. Looks at the inputs alone."""
+    shared = ret_meets_ins = bc_meet = 0
+    for d in steps:
+        ka = {k for k, _, _ in d["A"]}
+        kb = {k for k, _, _ in d["B"]}
+        shared += bool(ka & kb)
+        for x, y in (("A", "B"), ("B", "A")):
+            neg = {k for k, _, m in d[x] if m < 0}
+            pos = {k for k, _, m in d[y] if m > 0}
+            ret_meets_ins += bool(neg & pos)
+        if stages == 2:
+            # a B delta and a C delta meeting through the same k3
+            bc_meet += bool({k3 for _, k3, _ in d["B"]}
+                            & {k3 for k3, _, _ in d["C"]})
+    assert 2 * shared >= len(steps), "bad seed: too few concurrent keys"
+    assert ret_meets_ins, "bad seed: no retraction meets an insert"
+    assert stages == 1 or bc_meet, "bad seed: no B/C delta meets on k3"
+
+
+@functools.lru_cache(maxsize=None)
+def _scenario(stages, seed, nsteps=6, nkeys=8, nvals=6, max_rows=32,
+              full=False):
+    """Seeded steps of concurrent deltas plus their reference: returns
+    (steps, want, final) with steps[i] = {relation: delta rows},
+    want[i] = naive(contents after step i) - naive(contents before) and
+    final = naive(final contents). Step 2 has an empty source delta
+    (lookup deltas only), step 4 a source delta only. Computed once per
+    scenario and shared, read-only, by the cases that use it."""
+    rng = np.random.default_rng(seed)
+    names = RELS[:stages + 1]
+    # B's val is k3, the next stage's key; a and c are payloads
+    val_range = {"A": nvals, "B": nkeys, "C": nvals}
+    contents = {r: Counter() for r in names}
+    steps, want = [], []
+    before = _naive_of(contents, stages)
+    for s in range(nsteps):
+        idle = {2: names[:1], 4: names[1:]}.get(s, ())
+        delta = {}
+        for r in names:
+            delta[r] = [] if r in idle else _gen_delta(
+                rng, contents[r], nkeys, val_range[r], max_rows, full)
+            for k, v, d in delta[r]:
+                contents[r][(k, v)] += d
+                assert contents[r][(k, v)] >= 0
+            contents[r] = +contents[r]
+        after = _naive_of(contents, stages)
+        steps.append(delta)
+        want.append(_minus(after, before))
+        before = after
+    _check_inputs(steps, stages)
+    return steps, want, dict(before)
+
+
+def _upd_cols(rows, t):
+    n = len(rows)
+    k = np.array([r[0] for r in rows], np.int64)
+    v = np.array([r[1] for r in rows], np.int64)
+    d = np.array([r[2] for r in rows], np.int64)
+    return k, v.view(np.uint8), np.full(n, t, np.uint64), d
+
+
+def _drive(ctx, stages, steps, installed, source_installed=None):
+    """Run `steps` through op.step at t = 1, 2, ...; `installed` maps a
+    lookup relation to whether the driver installs its delta before the
+    call. A stage-0 lookup delta that is already installed has to drain
+    before the source delta goes in, so then the op installs the source;
+    otherwise the driver does by default, as shared state. Returns the
+    per-step output columns, as step() gave them."""
+    if source_installed is None:
+        source_installed = not installed["B"]
+    names = RELS[:stages + 1]
+    arrs = {r: ctx.arr_create(abi.schema(1, 8)) for r in names}
+    op = render_join(ctx, arrs, _plan(stages))
+    outs = []
+    for t, delta in enumerate(steps, 1):
+        src = _upd_cols(delta["A"], t)
+        if source_installed:
+            ctx.arr_insert(arrs["A"], abi.make_updates(*src, t, t + 1))
+        lds = {}
+        for r in names[1:]:
+            lu = abi.make_updates(*_upd_cols(delta[r], t), t, t + 1)
+            if installed[r]:
+                ctx.arr_insert(arrs[r], lu)
+            lds[r] = (lu, installed[r])
+        outs.append(op.step(t, src, lds, source_installed=source_installed))
+    return outs
+
+
+def _consolidated(cols, stages, t):
+    """Sum diffs per output row and drop zeros: the two probes of a stage
+    are concatenated unconsolidated and may hold cancelling rows."""
+    k, v, tm, d = cols
+    n = len(tm)
+    assert (np.asarray(tm) == t).all()
+    w = np.ascontiguousarray(v).view(np.int64).reshape(n, stages)
+    out = Counter()
+    for i in range(n):
+        out[(int(k[i]),) + tuple(int(x) for x in w[i])] += int(d[i])
+    return {r: m for r, m in out.items() if m}
+
+
+def _check_exactly_once(outs, want, final, stages):
+    acc = Counter()
+    for t, (cols, w) in enumerate(zip(outs, want), 1):
+        got = _consolidated(cols, stages, t)
+        assert got == w, f"step {t}: output delta != naive(after) - " \
+                         f"naive(before)"
+        acc.update(got)
+    assert {r: m for r, m in acc.items() if m} == final, "accumulated"
+
+
+def _flags(bits):
+    return dict(zip(RELS[1:], bits))
+
+
+def _id(bits):
+    return "-".join(f"{r}_{'installed' if b else 'pending'}"
+                    for r, b in zip(RELS[1:], bits))
+
+
+# source_installed=None: the driver installs the source exactly when the
+# stage-0 lookup delta is pending; False: the op installs both
+SINGLE = [pytest.param((False,), None, id="B_pending-A_installed"),
+          pytest.param((False,), False, id="B_pending-A_pending"),
+          pytest.param((True,), None, id="B_installed-A_pending")]
+CHAIN = [pytest.param(b, id=_id(b)) for b in
+         ((False, False), (True, True), (False, True), (True, False))]
+SEED1, SEED2, SEED_BIG = 3, 4, 6
+BIG = dict(nsteps=3, nkeys=200, nvals=1000, max_rows=2000, full=True)
+
+
+@pytest.mark.parametrize("installed", [False, True])
+def test_minimal_concurrent_pair_counted_once(installed):
+    """One row on each side under the same key at the same time: the
+    pair is emitted with multiplicity exactly 1."""
+    from pyoracle import OracleCtx
+    ctx = OracleCtx()
+    steps = [{"A": [(3, 7, 1)], "B": [(3, 5, 1)]}]
+    (cols,) = _drive(ctx, 1, steps, {"B": installed})
+    ctx.close()
+    assert _consolidated(cols, 1, 1) == {(5, 7): 1}
+    assert np.asarray(cols[3]).tolist() == [1]
+
+
+def test_both_deltas_installed_is_rejected():
+    """Source and stage-0 lookup delta both installed by the caller: no
+    probe order counts their pairs once, so step() refuses — unless one
+    of the two deltas is empty and there is no pair."""
+    from pyoracle import OracleCtx
+    ctx = OracleCtx()
+    arrs = {r: ctx.arr_create(abi.schema(1, 8)) for r in RELS[:2]}
+    op = render_join(ctx, arrs, _plan(1))
+    src = _upd_cols([(3, 7, 1)], 1)
+    lu = abi.make_updates(*_upd_cols([(3, 5, 1)], 1), 1, 2)
+    ctx.arr_insert(arrs["A"], abi.make_updates(*src, 1, 2))
+    ctx.arr_insert(arrs["B"], lu)
+    with pytest.raises(ValueError):
+        op.step(1, src, {"B": (lu, True)})
+    # t=2: only B changes, pre-installed; the source delta is empty
+    lu2 = abi.make_updates(*_upd_cols([(3, 6, 2)], 2), 2, 3)
+    ctx.arr_insert(arrs["B"], lu2)
+    cols = op.step(2, _upd_cols([], 2), {"B": (lu2, True)})
+    ctx.close()
+    assert _consolidated(cols, 1, 2) == {(6, 7): 2}
+
+
+@pytest.mark.parametrize("bits,source_installed", SINGLE)
+def test_single_stage_concurrent_deltas_oracle(bits, source_installed):
+    from pyoracle import OracleCtx
+    steps, want, final = _scenario(1, SEED1)
+    ctx = OracleCtx()
+    outs = _drive(ctx, 1, steps, _flags(bits), source_installed)
+    ctx.close()
+    _check_exactly_once(outs, want, final, 1)
+
+
+@pytest.mark.parametrize("bits", CHAIN)
+def test_two_stage_concurrent_deltas_oracle(bits):
+    from pyoracle import OracleCtx
+    steps, want, final = _scenario(2, SEED2)
+    ctx = OracleCtx()
+    outs = _drive(ctx, 2, steps, _flags(bits))
+    ctx.close()
+    _check_exactly_once(outs, want, final, 2)
+
+
+def _gpu_case(stages, scenario, bits, source_installed=None):
+    """Same driver on the engine and the oracle: bit-exact per step (each
+    probe's output is consolidated, so the row order is defined), and the
+    engine's output held to the naive reference."""
+    from materialize_amd._ffi import GpuCtx
+    from pyoracle import OracleCtx
+    steps, want, final = scenario
+    g, o = GpuCtx(), OracleCtx()
+    og = _drive(g, stages, steps, _flags(bits), source_installed)
+    oo = _drive(o, stages, steps, _flags(bits), source_installed)
+    g.close()
+    o.close()
+    for t, (cg, co) in enumerate(zip(og, oo), 1):
+        for x, y, what in zip(cg, co, COLS):
+            np.testing.assert_array_equal(np.asarray(x).view(np.uint8),
+                                          np.asarray(y).view(np.uint8),
+                                          err_msg=f"step {t} {what}")
+    _check_exactly_once(og, want, final, stages)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bits,source_installed", SINGLE)
+def test_single_stage_concurrent_deltas_gpu(bits, source_installed):
+    _gpu_case(1, _scenario(1, SEED1), bits, source_installed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bits", CHAIN)
+def test_two_stage_concurrent_deltas_gpu(bits):
+    _gpu_case(2, _scenario(2, SEED2), bits)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bits", [(False,), (True,)],
+                         ids=["B_pending", "B_installed"])
+def test_single_stage_concurrent_deltas_gpu_2000_rows(bits):
+    """2,000 rows per delta over 200 keys: the probe's queue reservation
+    spans more than one wave and more than one workgroup."""
+    _gpu_case(1, _scenario(1, SEED_BIG, **BIG), bits)
