@@ -168,7 +168,28 @@ typedef struct {
   uint8_t  width;    /* 4 or 8                                         */
   uint8_t  is_float; /* datum is f64 (for SUM_F64)                     */
   uint8_t  nullable; /* datum has a null indicator byte at off+width   */
+  uint8_t  distinct; /* COUNT/SUM(DISTINCT x), see below. Occupies the
+                        struct's former padding byte: sizeof stays 8 and 0
+                        is the plain aggregate                            */
 } mz_gpu_aggregate;
+
+/* distinct = 1 — AccumulablePlan::distinct_aggrs (plan/reduce.rs:233,
+ * rendered by build_accumulable, render/reduce.rs:1357-1581, which keeps
+ * one distinct arrangement of (key, datum) per such aggregate): the
+ * aggregate sees each distinct datum of a key once, for as long as the net
+ * multiplicity of (key, datum) is nonzero. The operator keeps a resident
+ * (key, datum) count table per distinct aggregate and feeds the accumulator
+ * only the presence changes (±1) of those pairs.
+ *   - MZ_AGG_COUNT / MZ_AGG_SUM_I64 over a 4- or 8-byte signed LE datum at
+ *     `off` (inside in.val_bytes), sign-extended to i64; distinctness is
+ *     equality of that i64. `nullable` is honoured: a NULL datum
+ *     contributes nothing; a key whose datums are all NULL finalizes
+ *     SUM(DISTINCT) to the NULL slot and COUNT(DISTINCT) to 0.
+ *   - MZ_AGG_MIN_I64 / MZ_AGG_MAX_I64 accept the flag and ignore it.
+ *   - MZ_AGG_SUM_F64 or is_float with distinct is rejected at create time
+ *     (float Datum equality is not byte equality).
+ * The per-key row count that decides key existence and "all NULL -> NULL"
+ * stays the net input row count. */
 
 #define MZ_GPU_MAX_AGGS 4
 

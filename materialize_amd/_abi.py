@@ -103,6 +103,8 @@ class Aggregate(C.Structure):
         ("width", C.c_uint8),
         ("is_float", C.c_uint8),
         ("nullable", C.c_uint8),
+        # COUNT/SUM(DISTINCT x); sits in the struct's former padding byte
+        ("distinct", C.c_uint8),
     ]
 
 
@@ -294,10 +296,34 @@ def topk_spec(in_schema, order, offset=0, limit=-1):
     return sp
 
 
+def is_distinct(agg):
+    """COUNT/SUM(DISTINCT x). MIN/MAX carry the flag without effect: the
+    extremum of a set is that of the multiset."""
+    return bool(agg.distinct) and agg.func in (MZ_AGG_COUNT, MZ_AGG_SUM_I64,
+                                               MZ_AGG_SUM_F64)
+
+
+def _check_distinct(who, i, a, in_schema):
+    """The create-time rules for a distinct aggregate (mz_gpu.h), checked
+    here as well as in the C layer (ValueError)."""
+    if not is_distinct(a):
+        return
+    if a.func == MZ_AGG_SUM_F64 or a.is_float:
+        raise ValueError(f"{who}: aggregate {i}: DISTINCT over a float "
+                         "datum is unsupported")
+    if a.width not in (4, 8):
+        raise ValueError(f"{who}: aggregate {i}: DISTINCT datum width must "
+                         "be 4 or 8")
+    if a.off + a.width + (1 if a.nullable else 0) > in_schema.val_bytes:
+        raise ValueError(f"{who}: aggregate {i}: DISTINCT datum reads past "
+                         f"in.val_bytes ({in_schema.val_bytes})")
+
+
 def reduce_spec(aggs, in_schema):
     sp = ReduceSpec()
     sp.n_aggs = len(aggs)
     for i, a in enumerate(aggs):
+        _check_distinct("reduce", i, a, in_schema)
         sp.aggs[i] = a
     sp.in_ = in_schema
     sp.out = Schema(key_words=in_schema.key_words,
@@ -336,6 +362,7 @@ def collation_spec(aggs, in_schema, buckets=(256, 16, 1)):
         if is_hierarchical(a) and a.nullable:
             raise ValueError(f"collation: aggregate {i}: nullable MIN/MAX "
                              "inputs unsupported")
+        _check_distinct("collation", i, a, in_schema)
         if a.func == MZ_AGG_COUNT and not a.nullable:
             continue  # COUNT(*) reads nothing
         if a.width not in (4, 8):

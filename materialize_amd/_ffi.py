@@ -158,6 +158,10 @@ class GpuCtx:
     """One engine context on one GPU (one driver thread per GPU —
     mirrors a timely worker, server.rs:327-377)."""
 
+    # COUNT/SUM(DISTINCT x) (Aggregate.distinct) is implemented here; the
+    # render layer refuses such plans on contexts that do not say so.
+    supports_distinct_aggs = True
+
     def __init__(self, device=0):
         self.lib = load()
         from ._abi import Cfg
@@ -287,6 +291,10 @@ class GpuCtx:
         self._check(self.lib.mz_gpu_reduce_push(self.ctx, op, C.byref(upd),
                                                 C.byref(outp)))
         return self._take(outp)
+
+    def reduce_drop(self, op):
+        """Free the operator, its accumulator table and pair tables."""
+        self.lib.mz_gpu_reduce_drop(self.ctx, op)
 
     def arr_insert_async(self, arr, upd):
         self._check(self.lib.mz_gpu_arr_insert_async(self.ctx, arr,

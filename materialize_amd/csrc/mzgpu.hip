@@ -1442,6 +1442,191 @@ __global__ void k_threshold_apply(const u64 *ckeys, u32 kw2,
   }
 }
 
+// ---- DISTINCT aggregates (AccumulablePlan::distinct_aggrs; the reference
+// keeps one distinct (key, datum) arrangement per such aggregate and feeds
+// the accumulator its presence changes, reduce.rs:1357-1581). Here: one
+// resident pair table per distinct aggregate — a RedState keyed by
+// [key words][datum i64] with one wrapping count word, the threshold table
+// with kw2 = kw + 1 — and a key stage that folds the pairs' presence deltas
+// instead of the raw rows.
+
+// True for the aggregates that take the pair path (MIN/MAX ignore the flag).
+__host__ __device__ inline bool agg_is_distinct(const mz_gpu_aggregate &a) {
+  return a.distinct && a.func <= MZ_AGG_SUM_F64;
+}
+
+// Project (key, datum) of every staged row into a combined key row. A NULL
+// datum is neutralized — datum 0 with diff 0 — rather than dropped, so the
+// pair stream keeps the input's row count and time slices, and every key
+// of a main slice is a key of the pair slice.
+__global__ void k_pair_project(const u64 *keys, u32 kw, const u8 *vals,
+                               u32 vb, const i64 *diffs, u64 n,
+                               mz_gpu_aggregate a, u64 *ck, i64 *pdiffs) {
+  GRID_STRIDE(i, n) {
+    const u8 *v = vals + i * vb;
+    bool null = a.nullable && v[a.off + a.width] != 0;
+    u64 *dst = ck + i * (kw + 1);
+    for (u32 w = 0; w < kw; w++) dst[w] = keys[i * kw + w];
+    dst[kw] = null ? 0 : (u64)d_read_int(v + a.off, a.width);
+    pdiffs[i] = null ? 0 : diffs[i];
+  }
+}
+
+// Pair apply: one thread per (key, datum) group of a time slice. Folds the
+// group's diffs into the resident count and leaves the pair's presence
+// change (new != 0) - (old != 0) in delta[g]; the key stage reads it in a
+// later launch (RedState coherence rule), so no queue and no atomics.
+__global__ void k_pair_apply(const i64 *diffs, const u32 *gstart,
+                             const u32 *gidn, u64 m, RedState st,
+                             const u32 *found, const u32 *miss,
+                             const u32 *misspos, const u64 *d_nrows,
+                             int *delta) {
+  u64 G = m ? gidn[m - 1] : 0;
+  u64 base = *d_nrows;
+  GRID_STRIDE(g, G) {
+    u64 lo = gstart[g];
+    u64 end = (g + 1 < G) ? gstart[g + 1] : m;
+    u64 idx = miss[g] ? base + misspos[g] : found[g];
+    if (idx >= st.capacity) {  // overflow flagged by insert
+      delta[g] = 0;
+      continue;
+    }
+    i64 *cnt = (i64 *)(st.rows + idx * st.stride_w + (st.stride_w - 1));
+    i64 old = *cnt, nw = old;
+    for (u64 r = lo; r < end; r++) nw = wadd(nw, diffs[r]);
+    *cnt = nw;
+    delta[g] = (nw != 0 ? 1 : 0) - (old != 0 ? 1 : 0);
+  }
+}
+
+// One distinct aggregate's pair groups of the current slice, as the key
+// stage reads them: combined key rows (kw + 1 words, sorted), group starts,
+// the inclusive group-id scan (its last entry is the group count) and the
+// presence deltas. ck == nullptr: the aggregate is not distinct.
+struct PairView {
+  const u64 *ck;
+  const u32 *gstart;
+  const u32 *gidn;
+  const int *delta;
+};
+struct PairViews {
+  PairView v[MZ_GPU_MAX_AGGS];
+};
+
+// Phase C for operators with distinct aggregates: k_reduce_apply's loop
+// and output contract, one thread per changed key. Plain aggregates and
+// `total` fold the key's input rows; a distinct aggregate folds
+// datum_to_accumulator(datum) * delta over the key's pair groups, which
+// are contiguous and key-ordered like the main slice (lower-bound search;
+// an all-NULL key finds only its neutral (key, 0) group, delta 0).
+__global__ void __launch_bounds__(BLK)
+k_reduce_apply_distinct(const u64 *keys, const u8 *vals, u32 kw, u32 vb,
+                        const i64 *diffs, const u32 *gstart,
+                        const u32 *gidn, u64 hi_row, u64 t, RedState st,
+                        const u32 *found, const u32 *miss,
+                        const u32 *misspos, const u64 *d_nrows,
+                        mz_gpu_reduce_spec spec, PairViews pvs, u64 *okeys,
+                        u8 *ovals, u64 *otimes, i64 *odiffs,
+                        unsigned long long *ocount) {
+  u32 na = spec.n_aggs;
+  u32 ovb = spec.out.val_bytes;
+  u32 kw2 = kw + 1;
+  u64 G = hi_row ? gidn[hi_row - 1] : 0;
+  u64 base = *d_nrows;
+  u64 stride = (u64)gridDim.x * blockDim.x;
+  u64 start0 = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  u64 iters = (G + stride - 1) / stride;
+  u32 lane = threadIdx.x & 63;
+  for (u64 it = 0; it < iters; it++) {
+    u64 g = start0 + it * stride;
+    bool oe = false, ne = false;
+    const u64 *key = nullptr;
+    u8 oldrow[MZ_GPU_MAX_AGGS * 24], newrow[MZ_GPU_MAX_AGGS * 24];
+    if (g < G) {
+      u64 lo = gstart[g];
+      u64 end = (g + 1 < G) ? gstart[g + 1] : hi_row;
+      key = keys + lo * kw;
+      u64 idx = miss[g] ? base + misspos[g] : found[g];
+      if (idx < st.capacity) {  // overflow flagged by insert
+        u64 *row = st.rows + idx * st.stride_w;
+        i64 *total_p = (i64 *)(row + kw);
+        Acc5 *accs = (Acc5 *)(row + kw + 1);
+        i64 old_total = *total_p, new_total = old_total;
+        for (u64 r = lo; r < end; r++) new_total = wadd(new_total, diffs[r]);
+        *total_p = new_total;
+        oe = old_total != 0;
+        ne = new_total != 0;
+        for (u32 a = 0; a < na; a++) {
+          const mz_gpu_aggregate ag = spec.aggs[a];
+          const Acc5 old_a = accs[a];
+          Acc5 acc = old_a;
+          const PairView pv = pvs.v[a];
+          if (pv.ck) {
+            // the key's pair groups: [first group with key >= ours, while
+            // the key matches)
+            u64 Gp = pv.gidn[hi_row - 1];
+            u64 l = 0, h = Gp;
+            while (l < h) {
+              u64 mid = (l + h) >> 1;
+              if (d_key_cmp(pv.ck + (u64)pv.gstart[mid] * kw2, key, kw) < 0)
+                l = mid + 1;
+              else
+                h = mid;
+            }
+            for (u64 p = l; p < Gp; p++) {
+              const u64 *pk = pv.ck + (u64)pv.gstart[p] * kw2;
+              if (d_key_cmp(pk, key, kw) != 0) break;
+              i64 dl = pv.delta[p];
+              if (!dl) continue;
+              // datum_to_accumulator of a non-null integer datum
+              if (ag.func == MZ_AGG_SUM_I64)
+                acc.accum += (u128)(i128)(i64)pk[kw] * (u128)(i128)dl;
+              acc.nn += (u64)dl;
+            }
+          } else {
+            for (u64 r = lo; r < end; r++) {
+              i64 d = diffs[r];
+              Acc5 c = d_datum_to_acc(ag, vals + r * vb);
+              acc.accum += c.accum * (u128)(i128)d;
+              acc.nn += (u64)c.nn * (u64)d;
+              acc.pi += (u64)c.pi * (u64)d;
+              acc.ni += (u64)c.ni * (u64)d;
+              acc.nan += (u64)c.nan * (u64)d;
+            }
+          }
+          accs[a] = acc;
+          // exists = any nonzero component, as in k_reduce_apply
+          oe |= old_a.accum != 0 || old_a.nn || old_a.pi || old_a.ni ||
+                old_a.nan;
+          ne |= acc.accum != 0 || acc.nn || acc.pi || acc.ni || acc.nan;
+          d_finalize(ag, old_a, old_total, oldrow + 24 * a);
+          d_finalize(ag, acc, new_total, newrow + 24 * a);
+        }
+        if (oe && ne) {
+          bool same = true;
+          for (u32 c = 0; c < ovb; c++) same &= oldrow[c] == newrow[c];
+          if (same) oe = ne = false;
+        }
+      }
+    }
+    u32 c = (oe ? 1u : 0u) + (ne ? 1u : 0u);
+    u64 o = wave_reserve(ocount, c, lane);
+    if (oe) {
+      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
+      for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = oldrow[cb];
+      otimes[o] = t;
+      odiffs[o] = -1;
+      o++;
+    }
+    if (ne) {
+      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
+      for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = newrow[cb];
+      otimes[o] = t;
+      odiffs[o] = 1;
+    }
+  }
+}
+
 // ------------------------------------------------------------- topk
 // Compact one row per distinct group of a sorted slice (group key list
 // for the eval probes).
@@ -1975,6 +2160,13 @@ struct mz_gpu_red {
   u64 n_rows = 0;   // host mirror (minmax path); the reduce path keeps the
   u64 *d_nrows = nullptr;  // authoritative count on device (no readback)
   u64 *d_err = nullptr;
+  // DISTINCT aggregates: one resident (key, datum) -> count table each,
+  // in spec order of the distinct aggregates (see k_pair_apply)
+  u32 n_dist = 0;
+  u32 dist_agg[MZ_GPU_MAX_AGGS];     // index into spec.aggs
+  RedState pst[MZ_GPU_MAX_AGGS];
+  u64 p_nrows[MZ_GPU_MAX_AGGS] = {};  // host mirrors of d_pnrows[j]
+  u64 *d_pnrows = nullptr;            // [n_dist] row counts on device
 };
 
 // Threshold operator (render/threshold.rs:34-51): net count per (key,val)
@@ -3659,6 +3851,32 @@ static void arr_flush_impl(Ctx *ctx, mz_gpu_arr *a);
 // sub-reduce lives in ctx->reds); defined with the operator
 static void collation_free(mz_gpu_ctx *c, mz_gpu_collation *op);
 
+// The reduce operator's device state: accumulator table, counters and the
+// distinct aggregates' pair tables.
+static void red_free_state(Ctx *ctx, mz_gpu_red *r) {
+  for (void *p : {(void *)r->st.hash, (void *)r->st.rows, (void *)r->d_nrows,
+                  (void *)r->d_err, (void *)r->d_pnrows})
+    dfree(ctx, p);
+  for (u32 j = 0; j < r->n_dist; j++) {
+    dfree(ctx, r->pst[j].hash);
+    dfree(ctx, r->pst[j].rows);
+  }
+}
+
+// Create-time rules for a distinct aggregate (mz_gpu.h); nullptr = ok.
+static const char *distinct_agg_error(const mz_gpu_aggregate &g,
+                                      const mz_gpu_schema &in) {
+  if (!agg_is_distinct(g)) return nullptr;
+  if (g.func == MZ_AGG_SUM_F64 || g.is_float)
+    return "DISTINCT over a float datum is unsupported (float Datum "
+           "equality is not byte equality)";
+  if (g.width != 4 && g.width != 8)
+    return "DISTINCT datum width must be 4 or 8";
+  if ((u64)g.off + g.width + (g.nullable ? 1 : 0) > in.val_bytes)
+    return "DISTINCT datum reads past in.val_bytes";
+  return nullptr;
+}
+
 extern "C" {
 
 mz_gpu_ctx *mz_gpu_init(const mz_gpu_cfg *cfg) {
@@ -3781,9 +3999,7 @@ void mz_gpu_fini(mz_gpu_ctx *c) {
   ctx->arrs.clear();
   for (mz_gpu_red *r : ctx->reds) {
     if (dbg) fprintf(stderr, "[fini] red %p\n", (void *)r);
-    for (void *p : {(void *)r->st.hash, (void *)r->st.rows,
-                    (void *)r->d_nrows, (void *)r->d_err})
-      dfree(ctx, p);
+    red_free_state(ctx, r);
     delete r;
   }
   ctx->reds.clear();
@@ -4812,6 +5028,11 @@ mz_gpu_red *mz_gpu_reduce_create(mz_gpu_ctx *c,
                  "go through mz_gpu_collation_create";
       return nullptr;
     }
+  for (u32 a = 0; a < spec->n_aggs; a++)
+    if (const char *msg = distinct_agg_error(spec->aggs[a], spec->in)) {
+      ctx->err = std::string("reduce: ") + msg;
+      return nullptr;
+    }
   mz_gpu_red *r = new mz_gpu_red();
   r->spec = *spec;
   u32 kw = spec->in.key_words;
@@ -4830,15 +5051,30 @@ mz_gpu_red *mz_gpu_reduce_create(mz_gpu_ctx *c,
   fill_u64(ctx, r->d_nrows, 1, 0);
   fill_u64(ctx, r->d_err, 1, 0);
   fill_u64(ctx, r->st.hash, slots * (kw + 1), ~0ull);
+  // pair tables: [key kw][datum][count], same initial capacity
+  for (u32 a = 0; a < spec->n_aggs; a++)
+    if (agg_is_distinct(spec->aggs[a])) r->dist_agg[r->n_dist++] = a;
+  if (r->n_dist) {
+    u32 kw2 = kw + 1;
+    r->d_pnrows = dnew<u64>(ctx, r->n_dist);
+    fill_u64(ctx, r->d_pnrows, r->n_dist, 0);
+    for (u32 j = 0; j < r->n_dist; j++) {
+      RedState &ps = r->pst[j];
+      ps.slots = slots;
+      ps.capacity = cap;
+      ps.stride_w = kw2 + 1;
+      ps.hash = dnew<u64>(ctx, slots * (kw2 + 1));
+      ps.rows = dnew<u64>(ctx, cap * ps.stride_w);
+      fill_u64(ctx, ps.hash, slots * (kw2 + 1), ~0ull);
+    }
+  }
   c->impl.reds.push_back(r);
   return r;
 }
 
 void mz_gpu_reduce_drop(mz_gpu_ctx *c, mz_gpu_red *r) {
   Ctx *ctx = &c->impl;
-  for (void *p : {(void *)r->st.hash, (void *)r->st.rows,
-                  (void *)r->d_nrows, (void *)r->d_err})
-    dfree(ctx, p);
+  red_free_state(ctx, r);
   auto &v = ctx->reds;
   v.erase(std::remove(v.begin(), v.end(), r), v.end());
   delete r;
@@ -4907,6 +5143,11 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
     red_compact_grow(ctx, op->st, op->d_nrows, op->n_rows, n, kw, kw);
     op->capacity = op->st.capacity;
   }
+  u32 kw2 = kw + 1;  // pair tables' combined key: [key words][datum]
+  for (u32 j = 0; j < op->n_dist; j++)
+    if (op->p_nrows[j] + n > op->pst[j].capacity)
+      red_compact_grow(ctx, op->pst[j], op->d_pnrows + j, op->p_nrows[j], n,
+                       kw2, kw2);
   if (n == 0) {
     *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1), dnew<u64>(ctx, 1),
                     dnew<i64>(ctx, 1), 0, okw, ovb);
@@ -4960,8 +5201,62 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
   fill_u64(ctx, (u64 *)ocount, 1, 0);
   u32 *flags = (u32 *)S.get(n * 4);
   u32 *gid = (u32 *)S.get(n * 4);
+  // DISTINCT aggregates: the (key, datum) stream of each, sorted by
+  // (time, key, datum). NULL datums stay as neutral rows, so the sorted
+  // times equal stm and the slices below cut both streams alike.
+  u64 *psk[MZ_GPU_MAX_AGGS];
+  i64 *psd[MZ_GPU_MAX_AGGS];
+  for (u32 j = 0; j < op->n_dist; j++) {
+    u64 *ck = (u64 *)S.get(n * kw2 * 8);
+    i64 *pdf = (i64 *)S.get(n * 8);
+    hipLaunchKernelGGL(k_pair_project, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, d.keys, kw, d.vals, vb, d.diffs, n,
+                       op->spec.aggs[op->dist_agg[j]], ck, pdf);
+    u32 *pperm = (u32 *)S.get(n * 4);
+    sort_updates(ctx, ck, kw2, nullptr, 0, d.times, n, pperm, true);
+    psk[j] = (u64 *)S.get(n * kw2 * 8);
+    psd[j] = (i64 *)S.get(n * 8);
+    hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, ck, kw2, pperm, psk[j], n);
+    hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, pdf, pperm, psd[j], n);
+  }
   for (auto [lo, hi] : slices) {
     u64 m = hi - lo;
+    // Pair stage: fold the slice into each pair table and leave one
+    // presence delta per (key, datum) group for the key stage, which runs
+    // in a later launch than every pair apply it reads.
+    PairViews pvs{};
+    for (u32 j = 0; j < op->n_dist; j++) {
+      const u64 *pck = psk[j] + lo * kw2;
+      u32 *pflags = (u32 *)S.get(m * 4);
+      u32 *pgid = (u32 *)S.get(m * 4);
+      u32 *pstarts = (u32 *)S.get(m * 4);
+      hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, pck, kw2, stm + lo, pflags, m);
+      inclusive_scan_u32(ctx, pflags, pgid, m);
+      hipLaunchKernelGGL(k_group_starts, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, pflags, pgid, pstarts, m);
+      u32 *pfound = (u32 *)S.get(m * 4);
+      u32 *pmiss = (u32 *)S.get(m * 4);
+      hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, pck, kw2, pstarts, 0, pgid, m,
+                         op->pst[j], pfound, pmiss);
+      u32 *pmisspos = (u32 *)S.get((m + 1) * 4);
+      exclusive_scan_u32_ns(ctx, pmiss, pmisspos, m);
+      hipLaunchKernelGGL(k_red_insert, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, pck, kw2, pstarts, 0, pgid, m, pmiss,
+                         pmisspos, 0, op->d_pnrows + j, op->d_err,
+                         op->pst[j]);
+      int *pdelta = (int *)S.get(m * 4);
+      hipLaunchKernelGGL(k_pair_apply, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, psd[j] + lo, pstarts, pgid, m,
+                         op->pst[j], pfound, pmiss, pmisspos,
+                         op->d_pnrows + j, pdelta);
+      hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
+                         op->d_pnrows + j, pmisspos, pgid, m);
+      pvs.v[op->dist_agg[j]] = PairView{pck, pstarts, pgid, pdelta};
+    }
     // key-group starts within the slice (group count stays on device)
     hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
                        ctx->stream, sk + lo * kw, kw, stm + lo, flags, m);
@@ -5047,12 +5342,20 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
     hipLaunchKernelGGL(k_red_insert, dim3(ngrid(m)), dim3(BLK), 0,
                        ctx->stream, sk + lo * kw, kw, starts, 0, gid, m,
                        miss, misspos, 0, op->d_nrows, op->d_err, op->st);
-    hipLaunchKernelGGL(k_reduce_apply, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, sv + lo * vb, kw, vb,
-                       sd + lo, starts, 0, gid, m,
-                       htimes[htimes.size() == 1 ? 0 : lo], op->st, found,
-                       miss, misspos, 0, op->d_nrows, op->spec, pk, pv, pt,
-                       pd, ocount);
+    if (op->n_dist)
+      hipLaunchKernelGGL(k_reduce_apply_distinct, dim3(ngrid(m)), dim3(BLK),
+                         0, ctx->stream, sk + lo * kw, sv + lo * vb, kw, vb,
+                         sd + lo, starts, gid, m,
+                         htimes[htimes.size() == 1 ? 0 : lo], op->st, found,
+                         miss, misspos, op->d_nrows, op->spec, pvs, pk, pv,
+                         pt, pd, ocount);
+    else
+      hipLaunchKernelGGL(k_reduce_apply, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, sk + lo * kw, sv + lo * vb, kw, vb,
+                         sd + lo, starts, 0, gid, m,
+                         htimes[htimes.size() == 1 ? 0 : lo], op->st, found,
+                         miss, misspos, 0, op->d_nrows, op->spec, pk, pv, pt,
+                         pd, ocount);
     hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
                        op->d_nrows, misspos, gid, m);
     if (getenv("MZ_DBG_SORT")) {
@@ -5110,9 +5413,13 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
                            hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipMemcpyAsync(stage + 2, op->d_nrows, 8,
                            hipMemcpyDeviceToHost, ctx->stream));
+  if (op->n_dist)  // the pair tables' mirrors ride the same readback
+    HIP_CHECK(hipMemcpyAsync(stage + 3, op->d_pnrows, 8 * op->n_dist,
+                             hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   u64 emitted = stage[0], errflag = stage[1];
   op->n_rows = stage[2];
+  for (u32 j = 0; j < op->n_dist; j++) op->p_nrows[j] = stage[3 + j];
   DevUpdates pin{pk, pv, pt, pd, (u64)emitted};
   u64 *ok;
   u8 *ov;
@@ -5925,6 +6232,10 @@ mz_gpu_collation *mz_gpu_collation_create(mz_gpu_ctx *c,
     bool mm = g.func >= MZ_AGG_MIN_I64;
     if (mm && g.nullable)
       return fail("collation: nullable MIN/MAX inputs unsupported");
+    if (const char *msg = distinct_agg_error(g, spec->in)) {
+      ctx->err = std::string("collation: ") + msg;
+      return nullptr;
+    }
     if (g.func != MZ_AGG_COUNT || g.nullable) {  // COUNT(*) reads nothing
       if (g.width != 4 && g.width != 8)
         return fail("collation: aggregate width must be 4 or 8");

@@ -421,13 +421,30 @@ class ReducePlan:
     spec: abi.ReduceSpec
 
 
+def _require_distinct_support(ctx, spec):
+    """COUNT/SUM(DISTINCT x) renders only on a context that implements it:
+    one without it (the CPU oracle) would silently compute the plain
+    aggregate."""
+    if any(abi.is_distinct(spec.aggs[i]) for i in range(spec.n_aggs)) \
+            and not getattr(ctx, "supports_distinct_aggs", False):
+        raise NotImplementedError(
+            "plan has a DISTINCT COUNT/SUM aggregate and this context does "
+            "not implement DISTINCT aggregates")
+
+
 class ReduceOp:
     def __init__(self, ctx, plan: ReducePlan):
+        _require_distinct_support(ctx, plan.spec)
         self.ctx = ctx
         self.op = ctx.reduce_create(plan.spec)
 
     def push(self, updates) -> DevOut:
         return self.ctx.reduce_push_dev(self.op, updates)
+
+    def drop(self):
+        if self.op is not None:
+            self.ctx.reduce_drop(self.op)
+            self.op = None
 
 
 @dataclass
@@ -444,6 +461,7 @@ class CollationOp:
     key in the SQL aggregate order. Single-timestamp pushes only."""
 
     def __init__(self, ctx, plan: CollationPlan):
+        _require_distinct_support(ctx, plan.spec)
         self.ctx = ctx
         self.op = ctx.collation_create(plan.spec)
 
@@ -460,8 +478,9 @@ def plan_reduce(aggs, in_schema, **kw):
     """Pick the reduce plan for `aggs` the way the reference does
     (ReducePlan::create_from, plan/reduce.rs): Collation only when more
     than one reduction type is present or the single type is hierarchical;
-    all-accumulable aggregates keep the plain ReducePlan. `kw` goes to
-    abi.collation_spec (e.g. buckets=...)."""
+    all-accumulable aggregates keep the plain ReducePlan, DISTINCT members
+    included (the reference's AccumulablePlan carries them as
+    distinct_aggrs). `kw` goes to abi.collation_spec (e.g. buckets=...)."""
     aggs = list(aggs)
     if any(abi.is_hierarchical(a) for a in aggs):
         return CollationPlan(abi.collation_spec(aggs, in_schema, **kw))
