@@ -1245,25 +1245,77 @@ __global__ void k_red_insert(const u64 *keys, u32 kw, const u32 *gstart,
   }
 }
 
+// ---- pieces shared by the two reduce apply kernels
+
+// acc += c * d, all five components (explode_one * diff + semigroup
+// merge; wrapping)
+__device__ __forceinline__ void acc_fold(Acc5 &acc, const Acc5 c, i64 d) {
+  acc.accum += c.accum * (u128)(i128)d;
+  acc.nn += (u64)c.nn * (u64)d;
+  acc.pi += (u64)c.pi * (u64)d;
+  acc.ni += (u64)c.ni * (u64)d;
+  acc.nan += (u64)c.nan * (u64)d;
+}
+
+// any component non-zero (reduce_abelian: keys with nonempty input
+// accumulation produce one output row)
+__device__ __forceinline__ bool acc_nonzero(const Acc5 &a) {
+  return a.accum != 0 || a.nn || a.pi || a.ni || a.nan;
+}
+
+// A key whose old and new rows both exist and finalize to the same bytes
+// emits nothing.
+__device__ __forceinline__ void cancel_unchanged(bool &oe, bool &ne,
+                                                 const u8 *oldrow,
+                                                 const u8 *newrow, u32 ovb) {
+  if (oe && ne) {
+    bool same = true;
+    for (u32 c = 0; c < ovb; c++) same &= oldrow[c] == newrow[c];
+    if (same) oe = ne = false;
+  }
+}
+
+// Emit the retraction of the old row and the assertion of the new one.
+// Every lane of the wave calls this once per iteration: ONE wave-aggregated
+// output reservation (per-row atomicAdds on the shared counter serialized
+// within each wave — same cure as the probe queues).
+__device__ __forceinline__ void emit_old_new(
+    bool oe, bool ne, const u64 *key, u32 kw, const u8 *oldrow,
+    const u8 *newrow, u32 ovb, u64 t, u32 lane, u64 *okeys, u8 *ovals,
+    u64 *otimes, i64 *odiffs, unsigned long long *ocount) {
+  u32 c = (oe ? 1u : 0u) + (ne ? 1u : 0u);
+  u64 o = wave_reserve(ocount, c, lane);
+  if (oe) {
+    for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
+    for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = oldrow[cb];
+    otimes[o] = t;
+    odiffs[o] = -1;
+    o++;
+  }
+  if (ne) {
+    for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
+    for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = newrow[cb];
+    otimes[o] = t;
+    odiffs[o] = 1;
+  }
+}
+
 // Phase C: one thread per distinct key in a time slice [lo,hi) of updates
 // sorted by (time, key). gstart: start row of each key group; emits
-// corrections (new minus old finalized rows).
+// corrections (new minus old finalized rows). Uniform-iteration loop so
+// the whole wave reaches emit_old_new together.
 __global__ void k_reduce_apply(const u64 *keys, const u8 *vals, u32 kw,
                                u32 vb, const i64 *diffs, const u32 *gstart,
-                               u64 G, const u32 *gidn, u64 hi_row, u64 t,
+                               const u32 *gidn, u64 hi_row, u64 t,
                                RedState st, const u32 *found,
                                const u32 *miss, const u32 *misspos,
-                               u64 base, const u64 *d_nrows,
-                               mz_gpu_reduce_spec spec, u64 *okeys, u8 *ovals,
-                               u64 *otimes, i64 *odiffs,
-                               unsigned long long *ocount) {
+                               const u64 *d_nrows, mz_gpu_reduce_spec spec,
+                               u64 *okeys, u8 *ovals, u64 *otimes,
+                               i64 *odiffs, unsigned long long *ocount) {
   u32 na = spec.n_aggs;
   u32 ovb = spec.out.val_bytes;
-  if (gidn) G = hi_row ? gidn[hi_row - 1] : 0;
-  if (d_nrows) base = *d_nrows;
-  // Uniform-iteration loop with ONE wave-aggregated output reservation
-  // per iteration (the per-row atomicAdds on the shared counter
-  // serialized within each wave — same cure as the probe queues).
+  u64 G = hi_row ? gidn[hi_row - 1] : 0;
+  u64 base = *d_nrows;
   u64 stride = (u64)gridDim.x * blockDim.x;
   u64 start0 = blockIdx.x * (u64)blockDim.x + threadIdx.x;
   u64 iters = (G + stride - 1) / stride;
@@ -1286,29 +1338,18 @@ __global__ void k_reduce_apply(const u64 *keys, const u8 *vals, u32 kw,
         i64 old_total = *total_p;
         Acc5 old_a[MZ_GPU_MAX_AGGS];
         for (u32 a = 0; a < na; a++) old_a[a] = accs[a];
-        // apply updates (explode_one * diff + semigroup merge; wrapping)
         for (u64 r = lo; r < end; r++) {
           i64 d = diffs[r];
           const u8 *v = vals + r * vb;
-          for (u32 a = 0; a < na; a++) {
-            Acc5 c = d_datum_to_acc(spec.aggs[a], v);
-            accs[a].accum += c.accum * (u128)(i128)d;
-            accs[a].nn += (u64)c.nn * (u64)d;
-            accs[a].pi += (u64)c.pi * (u64)d;
-            accs[a].ni += (u64)c.ni * (u64)d;
-            accs[a].nan += (u64)c.nan * (u64)d;
-          }
+          for (u32 a = 0; a < na; a++)
+            acc_fold(accs[a], d_datum_to_acc(spec.aggs[a], v), d);
           *total_p = wadd(*total_p, d);
         }
         i64 new_total = *total_p;
-        // exists = any nonzero component (reduce_abelian: keys with
-        // nonempty input accumulation produce one output row)
         auto exists = [&](const Acc5 *as, i64 tot) {
           if (tot != 0) return true;
           for (u32 a = 0; a < na; a++)
-            if (as[a].accum != 0 || as[a].nn || as[a].pi || as[a].ni ||
-                as[a].nan)
-              return true;
+            if (acc_nonzero(as[a])) return true;
           return false;
         };
         oe = exists(old_a, old_total);
@@ -1319,28 +1360,11 @@ __global__ void k_reduce_apply(const u64 *keys, const u8 *vals, u32 kw,
         if (ne)
           for (u32 a = 0; a < na; a++)
             d_finalize(spec.aggs[a], accs[a], new_total, newrow + 24 * a);
-        if (oe && ne) {
-          bool same = true;
-          for (u32 c = 0; c < ovb; c++) same &= oldrow[c] == newrow[c];
-          if (same) oe = ne = false;
-        }
+        cancel_unchanged(oe, ne, oldrow, newrow, ovb);
       }
     }
-    u32 c = (oe ? 1u : 0u) + (ne ? 1u : 0u);
-    u64 o = wave_reserve(ocount, c, lane);
-    if (oe) {
-      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
-      for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = oldrow[cb];
-      otimes[o] = t;
-      odiffs[o] = -1;
-      o++;
-    }
-    if (ne) {
-      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
-      for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = newrow[cb];
-      otimes[o] = t;
-      odiffs[o] = 1;
-    }
+    emit_old_new(oe, ne, key, kw, oldrow, newrow, ovb, t, lane, okeys, ovals,
+                 otimes, odiffs, ocount);
   }
 }
 
@@ -1584,46 +1608,20 @@ k_reduce_apply_distinct(const u64 *keys, const u8 *vals, u32 kw, u32 vb,
               acc.nn += (u64)dl;
             }
           } else {
-            for (u64 r = lo; r < end; r++) {
-              i64 d = diffs[r];
-              Acc5 c = d_datum_to_acc(ag, vals + r * vb);
-              acc.accum += c.accum * (u128)(i128)d;
-              acc.nn += (u64)c.nn * (u64)d;
-              acc.pi += (u64)c.pi * (u64)d;
-              acc.ni += (u64)c.ni * (u64)d;
-              acc.nan += (u64)c.nan * (u64)d;
-            }
+            for (u64 r = lo; r < end; r++)
+              acc_fold(acc, d_datum_to_acc(ag, vals + r * vb), diffs[r]);
           }
           accs[a] = acc;
-          // exists = any nonzero component, as in k_reduce_apply
-          oe |= old_a.accum != 0 || old_a.nn || old_a.pi || old_a.ni ||
-                old_a.nan;
-          ne |= acc.accum != 0 || acc.nn || acc.pi || acc.ni || acc.nan;
+          oe |= acc_nonzero(old_a);
+          ne |= acc_nonzero(acc);
           d_finalize(ag, old_a, old_total, oldrow + 24 * a);
           d_finalize(ag, acc, new_total, newrow + 24 * a);
         }
-        if (oe && ne) {
-          bool same = true;
-          for (u32 c = 0; c < ovb; c++) same &= oldrow[c] == newrow[c];
-          if (same) oe = ne = false;
-        }
+        cancel_unchanged(oe, ne, oldrow, newrow, ovb);
       }
     }
-    u32 c = (oe ? 1u : 0u) + (ne ? 1u : 0u);
-    u64 o = wave_reserve(ocount, c, lane);
-    if (oe) {
-      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
-      for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = oldrow[cb];
-      otimes[o] = t;
-      odiffs[o] = -1;
-      o++;
-    }
-    if (ne) {
-      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
-      for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = newrow[cb];
-      otimes[o] = t;
-      odiffs[o] = 1;
-    }
+    emit_old_new(oe, ne, key, kw, oldrow, newrow, ovb, t, lane, okeys, ovals,
+                 otimes, odiffs, ocount);
   }
 }
 
@@ -1651,15 +1649,6 @@ __global__ void k_init_minmax(u64 *mins, u64 *maxs, u64 n) {
   }
 }
 
-// diagnostic: kernel's-eye view of the hash slot a key probes first
-__global__ void k_dbg_read_slot(const u64 *hash, u64 slots, const u64 *key,
-                                u32 kw, u64 *out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    u64 h = route_hash(key, kw) & (slots - 1);
-    for (u32 w = 0; w < kw + 1; w++) out[w] = hash[h * (kw + 1) + w];
-    out[kw + 1] = h;
-  }
-}
 __global__ void k_fill_i64(i64 *p, u64 n, i64 v) { GRID_STRIDE(i, n) p[i] = v; }
 
 __global__ void k_check_pos(const i64 *d, u64 n, u64 *err) {
@@ -1981,7 +1970,7 @@ __global__ void __launch_bounds__(BLK) k_collate_apply(const u64 *skeys, u32 kw,
           mask |= 1ull << p;
         }
         if (mask != 0 && mask != full) bad = true;
-        if (mask == 0)  // dead row: reclaimable by red_compact_grow
+        if (mask == 0)  // dead row: reclaimable by kt_compact_grow
           for (u32 w = 0; w < L.PW; w++) pay[w] = 0;
         row[kw] = mask;
         if (bad) {
@@ -2153,34 +2142,42 @@ struct mz_gpu_join {
   mz_gpu_closure cl;
 };
 
+// A resident keyed table as an operator holds it: the RedState plus the row
+// counter the upsert protocol runs on (kt_* helpers).
+// Device-counted tables keep the authoritative count in *d_nrows — bumped
+// after each slice's apply, never read back mid-push — and n_rows mirrors
+// it from the push's closing readback to decide growth before the next
+// push. A host-counted table (minmax levels) has no device words and keeps
+// its count in n_rows alone.
+struct KeyedTable {
+  RedState st{};
+  u32 kw = 0;              // key words; a hash slot is kw + 1 words
+  u64 n_rows = 0;          // host mirror of *d_nrows
+  u64 *d_nrows = nullptr;  // device row counter
+  u64 *d_err = nullptr;    // device error word(s); [0] = capacity exceeded
+  bool owns_ctrs = false;  // d_nrows heads a block this table allocated
+};
+
 struct mz_gpu_red {
   mz_gpu_reduce_spec spec;
-  RedState st;
-  u64 capacity;
-  u64 n_rows = 0;   // host mirror (minmax path); the reduce path keeps the
-  u64 *d_nrows = nullptr;  // authoritative count on device (no readback)
-  u64 *d_err = nullptr;
+  // One counter block [key rows][err][pair rows * n_dist]: every table of
+  // the operator points into it, and a push reads it back in one copy.
+  u64 *d_ctr = nullptr;
+  KeyedTable tbl;  // accumulator table: [key kw][total][na * 6 words]
   // DISTINCT aggregates: one resident (key, datum) -> count table each,
   // in spec order of the distinct aggregates (see k_pair_apply)
   u32 n_dist = 0;
-  u32 dist_agg[MZ_GPU_MAX_AGGS];     // index into spec.aggs
-  RedState pst[MZ_GPU_MAX_AGGS];
-  u64 p_nrows[MZ_GPU_MAX_AGGS] = {};  // host mirrors of d_pnrows[j]
-  u64 *d_pnrows = nullptr;            // [n_dist] row counts on device
+  u32 dist_agg[MZ_GPU_MAX_AGGS];  // index into spec.aggs
+  KeyedTable ptbl[MZ_GPU_MAX_AGGS];
 };
 
 // Threshold operator (render/threshold.rs:34-51): net count per (key,val)
-// pair in a resident RedState table keyed by the combined
-// (key-words || val-words) row; corrections delta = pos(new) - pos(old).
+// pair in a resident table keyed by the combined (key-words || val-words)
+// row; corrections delta = pos(new) - pos(old).
 struct mz_gpu_thr {
   mz_gpu_schema s;
   u32 kw2;  // combined key words: key_words + ceil(val_bytes/8)
-  RedState st;
-  u64 capacity;
-  u64 n_rows = 0;  // host mirror of *d_nrows (refreshed at each push's
-                   // closing sync; drives compaction/growth pre-checks)
-  u64 *d_nrows = nullptr;
-  u64 *d_err = nullptr;
+  KeyedTable tbl;
 };
 
 // TopK operator (top_k.rs:322-418): the operator owns its input
@@ -2403,35 +2400,75 @@ static void fill_u8(Ctx *c, u8 *p, u64 n, u8 v) {
 
 u64 exclusive_scan_u32(Ctx *c, const u32 *in, u32 *out, u64 n);
 
-// Reclaim dead rows (all state words zero from `from_w` up) and grow the
-// table so `need` more rows fit: rebuild rows + hash at the new capacity.
-// Synchronizes. h_nrows is the op's host mirror of *d_nrows.
-static void red_compact_grow(Ctx *c, RedState &st, u64 *d_nrows,
-                             u64 &h_nrows, u64 need, u32 key_words,
-                             u32 from_w) {
+// ---- keyed-table lifecycle (struct KeyedTable; protocol: DESIGN.md §4a)
+
+// Create a table of `cap` rows of [key kw][payload_w words] whose counters
+// live where the caller says: words of an operator-owned block, or nullptr
+// for a host-counted table. The hash is filled with the ~0 sentinel by a
+// kernel (never a memset, see fill_u64).
+static void kt_create_at(Ctx *c, KeyedTable &T, u32 kw, u32 payload_w,
+                         u64 cap, u64 *d_nrows, u64 *d_err) {
+  T.kw = kw;
+  T.n_rows = 0;
+  T.d_nrows = d_nrows;
+  T.d_err = d_err;
+  T.st.slots = 2 * cap;
+  T.st.capacity = cap;
+  T.st.stride_w = kw + payload_w;
+  T.st.hash = dnew<u64>(c, T.st.slots * (kw + 1));
+  T.st.rows = dnew<u64>(c, cap * T.st.stride_w);
+  fill_u64(c, T.st.hash, T.st.slots * (kw + 1), ~0ull);
+}
+
+// Same, with the table's own zeroed counter block [rows][err * n_err].
+static void kt_create(Ctx *c, KeyedTable &T, u32 kw, u32 payload_w, u64 cap,
+                      u32 n_err = 1) {
+  u64 *ctr = dnew<u64>(c, 1 + n_err);
+  fill_u64(c, ctr, 1 + n_err, 0);
+  kt_create_at(c, T, kw, payload_w, cap, ctr, ctr + 1);
+  T.owns_ctrs = true;
+}
+
+static void kt_free(Ctx *c, KeyedTable &T) {
+  dfree(c, T.st.hash);
+  dfree(c, T.st.rows);
+  if (T.owns_ctrs) dfree(c, T.d_nrows);
+  T = KeyedTable();
+}
+
+// Initial capacity: the operator's default unless the env names one.
+static u64 kt_env_cap(const char *env, u64 dflt) {
+  const char *e = getenv(env);
+  return e ? (u64)atoll(e) : dflt;
+}
+
+// Reclaim dead rows (all payload words zero) and grow the table so `need`
+// more rows fit: rebuild rows + hash at the new capacity. Synchronizes.
+static void kt_compact_grow(Ctx *c, KeyedTable &T, u64 need) {
   auto &S = (*c->scr);
-  u64 n = h_nrows;
+  RedState &st = T.st;
+  u64 n = T.n_rows;
   u32 *flags = (u32 *)S.get(std::max<u64>(n, 1) * 4);
   u32 *pos = (u32 *)S.get((std::max<u64>(n, 1) + 1) * 4);
   u64 live = 0;
   if (n) {
     hipLaunchKernelGGL(k_row_live_flags, dim3(ngrid(n)), dim3(BLK), 0,
-                       c->stream, st.rows, st.stride_w, from_w, n, flags);
+                       c->stream, st.rows, st.stride_w, T.kw, n, flags);
     live = exclusive_scan_u32(c, flags, pos, n);  // syncs
   }
   u64 newcap = st.capacity;
   while (live + need > newcap) newcap *= 2;
   u64 slots = 2 * newcap;
   u64 *nrows_arr = dnew<u64>(c, newcap * st.stride_w);
-  u64 *nhash = dnew<u64>(c, slots * (key_words + 1));
-  fill_u64(c, nhash, slots * (key_words + 1), ~0ull);
+  u64 *nhash = dnew<u64>(c, slots * (T.kw + 1));
+  fill_u64(c, nhash, slots * (T.kw + 1), ~0ull);
   if (live) {
     hipLaunchKernelGGL(k_compact_rows, dim3(ngrid(n)), dim3(BLK), 0,
                        c->stream, st.rows, st.stride_w, n, flags, pos,
                        nrows_arr);
     hipLaunchKernelGGL(k_rehash_rows, dim3(ngrid(live)), dim3(BLK), 0,
-                       c->stream, nrows_arr, st.stride_w, key_words, live,
-                       nhash, slots);
+                       c->stream, nrows_arr, st.stride_w, T.kw, live, nhash,
+                       slots);
   }
   dfree(c, st.rows);
   dfree(c, st.hash);
@@ -2439,8 +2476,14 @@ static void red_compact_grow(Ctx *c, RedState &st, u64 *d_nrows,
   st.hash = nhash;
   st.capacity = newcap;
   st.slots = slots;
-  h_nrows = live;
-  fill_u64(c, d_nrows, 1, live);
+  T.n_rows = live;
+  fill_u64(c, T.d_nrows, 1, live);
+}
+
+// Before a push that can open at most n new rows: growth is decided here,
+// from the host mirror, so no push ever overflows in flight.
+static void kt_reserve(Ctx *c, KeyedTable &T, u64 n) {
+  if (T.n_rows + n > T.st.capacity) kt_compact_grow(c, T, n);
 }
 
 // Cached-plan validity: slot s covered iff [min,max] within the cached
@@ -2939,6 +2982,165 @@ void consolidate_dev(Ctx *c, u32 kw, u32 vb, DevUpdates in, u64 **okeys,
   u64 M = 0;
   M = *(u64 *)d2h_pinned(c, dcounts, 8);
   *out_n = M;
+}
+
+// ---- keyed-table push protocol. Every operator with a
+// resident table runs, per time slice of its sorted input: group_sorted,
+// kt_upsert, its own apply kernel, kt_commit. All scratch comes from
+// *c->scr at call time, so the helpers follow a ScrGuard.
+
+mz_gpu_out *empty_out(Ctx *c, u32 kw, u32 vb) {
+  return make_out(dnew<u64>(c, 1), (u8 *)dmalloc(c, 1), dnew<u64>(c, 1),
+                  dnew<i64>(c, 1), 0, kw, vb);
+}
+
+// Key groups of a slice of m rows sorted by (time, key): gid is the
+// inclusive group-id scan (gid[m-1] = the group count, which stays on the
+// device), starts[g] the first row of group g.
+struct Groups {
+  u32 *gid, *starts;
+};
+Groups group_sorted(Ctx *c, const u64 *keys, u32 kw, const u64 *times,
+                    u64 m) {
+  auto &S = (*c->scr);
+  u32 *flags = (u32 *)S.get(m * 4);
+  Groups g{(u32 *)S.get(m * 4), (u32 *)S.get(m * 4)};
+  hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
+                     c->stream, keys, kw, times, flags, m);
+  inclusive_scan_u32(c, flags, g.gid, m);
+  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(m)), dim3(BLK), 0, c->stream,
+                     flags, g.gid, g.starts, m);
+  return g;
+}
+
+// Phases A and B of the upsert, as two launches (RedState coherence rule):
+// look every group's key up, then insert the misses at row *d_nrows + miss
+// rank. The caller's apply kernel is phase C — a third launch, resolving
+// rows with the same rule — and kt_commit follows it.
+struct Upsert {
+  u32 *found, *miss, *misspos;
+};
+Upsert kt_upsert(Ctx *c, const KeyedTable &T, const u64 *keys, Groups g,
+                 u64 m) {
+  auto &S = (*c->scr);
+  Upsert u{(u32 *)S.get(m * 4), (u32 *)S.get(m * 4),
+           (u32 *)S.get((m + 1) * 4)};
+  hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(m)), dim3(BLK), 0, c->stream,
+                     keys, T.kw, g.starts, 0, g.gid, m, T.st, u.found,
+                     u.miss);
+  exclusive_scan_u32_ns(c, u.miss, u.misspos, m);
+  hipLaunchKernelGGL(k_red_insert, dim3(ngrid(m)), dim3(BLK), 0, c->stream,
+                     keys, T.kw, g.starts, 0, g.gid, m, u.miss, u.misspos, 0,
+                     T.d_nrows, T.d_err, T.st);
+  return u;
+}
+
+// After the apply kernel: the inserted rows join the count.
+void kt_commit(Ctx *c, const KeyedTable &T, Upsert u, Groups g, u64 m) {
+  hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, c->stream, T.d_nrows,
+                     u.misspos, g.gid, m);
+}
+
+// Time slices [lo, hi) at time t of n rows sorted by time. Boundaries are
+// found on the host (few distinct times per batch); a single-timestamp
+// batch (upper == lower + 1, the steady-state churn shape) needs neither
+// the copy nor the sync.
+struct TimeSlice {
+  u64 lo, hi, t;
+};
+std::vector<TimeSlice> time_slices(Ctx *c, const u64 *stm, u64 n, u64 lower,
+                                   u64 upper) {
+  if (upper <= lower + 1) return {{0, n, lower}};
+  std::vector<u64> htimes(n);
+  HIP_CHECK(hipMemcpyAsync(htimes.data(), stm, n * 8, hipMemcpyDeviceToHost,
+                           c->stream));
+  HIP_CHECK(hipStreamSynchronize(c->stream));
+  std::vector<TimeSlice> slices;
+  for (u64 i = 0; i < n;) {
+    u64 j = i;
+    while (j < n && htimes[j] == htimes[i]) j++;
+    slices.push_back({i, j, htimes[i]});
+    i = j;
+  }
+  return slices;
+}
+
+// Sort n updates by (time, key) and materialize the sorted columns in
+// scratch (vals only when vb != 0).
+struct SortedCols {
+  u64 *keys;
+  u8 *vals;
+  u64 *times;
+  i64 *diffs;
+};
+SortedCols sort_gather(Ctx *c, const u64 *keys, u32 kw, const u8 *vals,
+                       u32 vb, const u64 *times, const i64 *diffs, u64 n) {
+  auto &S = (*c->scr);
+  u32 *perm = (u32 *)S.get(n * 4);
+  sort_updates(c, keys, kw, vals, vb, times, n, perm, true);
+  SortedCols s{(u64 *)S.get(n * kw * 8), (u8 *)S.get(std::max<u64>(n * vb, 1)),
+               (u64 *)S.get(n * 8), (i64 *)S.get(n * 8)};
+  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
+                     c->stream, keys, kw, perm, s.keys, n);
+  if (vb)
+    hipLaunchKernelGGL(k_gather_valrows, dim3(ngrid(n)), dim3(BLK), 0,
+                       c->stream, vals, vb, perm, s.vals, n);
+  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     times, perm, s.times, n);
+  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     diffs, perm, s.diffs, n);
+  return s;
+}
+
+// Correction rows an apply kernel appends through *ocount.
+struct CorrBuf {
+  u64 *pk;
+  u8 *pv;
+  u64 *pt;
+  i64 *pd;
+  unsigned long long *ocount;
+  u32 kw, vb;
+};
+CorrBuf corr_alloc(Ctx *c, u64 cap_rows, u32 kw, u32 vb) {
+  CorrBuf b{dnew<u64>(c, cap_rows * kw),
+            (u8 *)dmalloc(c, std::max<u64>(cap_rows * vb, 1)),
+            dnew<u64>(c, cap_rows),
+            dnew<i64>(c, cap_rows),
+            (unsigned long long *)(*c->scr).get(8),
+            kw,
+            vb};
+  fill_u64(c, (u64 *)b.ocount, 1, 0);
+  return b;
+}
+void corr_free(Ctx *c, CorrBuf &b) {
+  for (void *p : {(void *)b.pk, (void *)b.pv, (void *)b.pt, (void *)b.pd})
+    dfree(c, p);
+}
+// The push's one readback and sync: h[0] = the emitted count, h[1..] =
+// n_ctr counter words from d_ctr (the operator's rows and err words). h is
+// the pinned page: read it before the next d2h_pinned.
+const u64 *corr_read(Ctx *c, const CorrBuf &b, const u64 *d_ctr, u32 n_ctr) {
+  u64 *stage = (u64 *)c->pin;
+  HIP_CHECK(hipMemcpyAsync(stage, b.ocount, 8, hipMemcpyDeviceToHost,
+                           c->stream));
+  HIP_CHECK(hipMemcpyAsync(stage + 1, d_ctr, 8 * n_ctr,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_CHECK(hipStreamSynchronize(c->stream));
+  return stage;
+}
+// Consolidate the emitted rows (the count came back with corr_read:
+// sorting the zero-padded capacity dominated this path) and free the
+// buffer; the result, or nullptr if the push failed.
+mz_gpu_out *corr_finish(Ctx *c, CorrBuf &b, u64 emitted, bool failed) {
+  DevUpdates pin{b.pk, b.pv, b.pt, b.pd, emitted};
+  u64 *ok, *ot, Mc;
+  u8 *ov;
+  i64 *od;
+  consolidate_dev(c, b.kw, b.vb, pin, &ok, &ov, &ot, &od, &Mc);
+  corr_free(c, b);
+  if (!failed) return make_out(ok, ov, ot, od, Mc, b.kw, b.vb);
+  for (void *p : {(void *)ok, (void *)ov, (void *)ot, (void *)od}) dfree(c, p);
+  return nullptr;
 }
 
 void free_batch(Ctx *c, DevBatch &b) {
@@ -3854,13 +4056,9 @@ static void collation_free(mz_gpu_ctx *c, mz_gpu_collation *op);
 // The reduce operator's device state: accumulator table, counters and the
 // distinct aggregates' pair tables.
 static void red_free_state(Ctx *ctx, mz_gpu_red *r) {
-  for (void *p : {(void *)r->st.hash, (void *)r->st.rows, (void *)r->d_nrows,
-                  (void *)r->d_err, (void *)r->d_pnrows})
-    dfree(ctx, p);
-  for (u32 j = 0; j < r->n_dist; j++) {
-    dfree(ctx, r->pst[j].hash);
-    dfree(ctx, r->pst[j].rows);
-  }
+  kt_free(ctx, r->tbl);
+  for (u32 j = 0; j < r->n_dist; j++) kt_free(ctx, r->ptbl[j]);
+  dfree(ctx, r->d_ctr);
 }
 
 // Create-time rules for a distinct aggregate (mz_gpu.h); nullptr = ok.
@@ -4655,8 +4853,7 @@ static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
   }
   u64 n = d.n;
   if (n == 0 || bl.n == 0) {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1), dnew<u64>(ctx, 1),
-                    dnew<i64>(ctx, 1), 0, okw, ovb);
+    *out = empty_out(ctx, okw, ovb);
     return 0;
   }
   // SORTED deltas probe large batches by merge scan (k_probe_merge:
@@ -4923,8 +5120,7 @@ int mz_gpu_halfjoin2(mz_gpu_ctx *c, mz_gpu_arr *lk1, int le1,
   DevUpdates d = stage_updates(ctx, u, kw, stream_vb);
   u64 n = d.n;
   if (n == 0 || bl1.n == 0 || bl2.n == 0) {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                    dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, okw, ovb);
+    *out = empty_out(ctx, okw, ovb);
     return 0;
   }
   int mode1 = le1 ? PM_HALF_LE : PM_HALF_LT;
@@ -5036,38 +5232,18 @@ mz_gpu_red *mz_gpu_reduce_create(mz_gpu_ctx *c,
   mz_gpu_red *r = new mz_gpu_red();
   r->spec = *spec;
   u32 kw = spec->in.key_words;
-  u64 cap = 1ull << 22;  // 4M keys default; grows on demand (see
-                         // red_compact_grow); env override for tests/tuning
-  if (const char *e = getenv("MZ_GPU_RED_CAP")) cap = (u64)atoll(e);
-  r->capacity = cap;
-  u64 slots = 2 * cap;
-  r->st.hash = dnew<u64>(ctx, slots * (kw + 1));
-  r->st.slots = slots;
-  r->st.stride_w = kw + 1 + 6 * spec->n_aggs;
-  r->st.rows = dnew<u64>(ctx, cap * r->st.stride_w);
-  r->st.capacity = cap;
-  r->d_nrows = dnew<u64>(ctx, 1);
-  r->d_err = dnew<u64>(ctx, 1);
-  fill_u64(ctx, r->d_nrows, 1, 0);
-  fill_u64(ctx, r->d_err, 1, 0);
-  fill_u64(ctx, r->st.hash, slots * (kw + 1), ~0ull);
-  // pair tables: [key kw][datum][count], same initial capacity
+  // 4M keys default; grows on demand (kt_reserve); env override for
+  // tests/tuning. Pair tables [key kw][datum][count] start at the same size.
+  u64 cap = kt_env_cap("MZ_GPU_RED_CAP", 1ull << 22);
   for (u32 a = 0; a < spec->n_aggs; a++)
     if (agg_is_distinct(spec->aggs[a])) r->dist_agg[r->n_dist++] = a;
-  if (r->n_dist) {
-    u32 kw2 = kw + 1;
-    r->d_pnrows = dnew<u64>(ctx, r->n_dist);
-    fill_u64(ctx, r->d_pnrows, r->n_dist, 0);
-    for (u32 j = 0; j < r->n_dist; j++) {
-      RedState &ps = r->pst[j];
-      ps.slots = slots;
-      ps.capacity = cap;
-      ps.stride_w = kw2 + 1;
-      ps.hash = dnew<u64>(ctx, slots * (kw2 + 1));
-      ps.rows = dnew<u64>(ctx, cap * ps.stride_w);
-      fill_u64(ctx, ps.hash, slots * (kw2 + 1), ~0ull);
-    }
-  }
+  r->d_ctr = dnew<u64>(ctx, 2 + r->n_dist);
+  fill_u64(ctx, r->d_ctr, 2 + r->n_dist, 0);
+  kt_create_at(ctx, r->tbl, kw, 1 + 6 * spec->n_aggs, cap, r->d_ctr,
+               r->d_ctr + 1);
+  for (u32 j = 0; j < r->n_dist; j++)
+    kt_create_at(ctx, r->ptbl[j], kw + 1, 1, cap, r->d_ctr + 2 + j,
+                 r->d_ctr + 1);
   c->impl.reds.push_back(r);
   return r;
 }
@@ -5137,73 +5313,22 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
   u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
   u32 okw = op->spec.out.key_words, ovb = op->spec.out.val_bytes;
   u64 n = d.n;
-  if (op->n_rows + n > op->capacity) {
-    // worst case every update opens a new group: reclaim zeroed rows and
-    // grow so the push cannot overflow (n_rows mirror from the last sync)
-    red_compact_grow(ctx, op->st, op->d_nrows, op->n_rows, n, kw, kw);
-    op->capacity = op->st.capacity;
-  }
-  u32 kw2 = kw + 1;  // pair tables' combined key: [key words][datum]
-  for (u32 j = 0; j < op->n_dist; j++)
-    if (op->p_nrows[j] + n > op->pst[j].capacity)
-      red_compact_grow(ctx, op->pst[j], op->d_pnrows + j, op->p_nrows[j], n,
-                       kw2, kw2);
+  // worst case every update opens a new group (and a new pair)
+  kt_reserve(ctx, op->tbl, n);
+  for (u32 j = 0; j < op->n_dist; j++) kt_reserve(ctx, op->ptbl[j], n);
   if (n == 0) {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1), dnew<u64>(ctx, 1),
-                    dnew<i64>(ctx, 1), 0, okw, ovb);
+    *out = empty_out(ctx, okw, ovb);
     return 0;
   }
-  // sort by (time, key)
-  u32 *perm = (u32 *)S.get(n * 4);
-  sort_updates(ctx, d.keys, kw, d.vals, vb, d.times, n, perm, true);
-  // materialize sorted columns
-  u64 *sk = (u64 *)S.get(n * kw * 8);
-  u8 *sv = (u8 *)S.get(std::max<u64>(n * vb, 1));
-  u64 *stm = (u64 *)S.get(n * 8);
-  i64 *sd = (i64 *)S.get(n * 8);
-  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
-                     ctx->stream, d.keys, kw, perm, sk, n);
-  if (vb)
-    hipLaunchKernelGGL(k_gather_valrows, dim3(ngrid(n)), dim3(BLK), 0,
-                       ctx->stream, d.vals, vb, perm, sv, n);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.times, perm, stm, n);
-  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.diffs, perm, sd, n);
-  // time slice boundaries (host; few distinct times per batch).
-  // Single-timestamp batches (upper == lower+1, the steady-state churn
-  // shape) skip the boundary copy entirely.
-  std::vector<u64> htimes;
-  std::vector<std::pair<u64, u64>> slices;  // (start, end)
-  if (upper <= lower + 1) {
-    htimes.assign(1, lower);
-    slices.push_back({0, n});
-  } else {
-    htimes.resize(n);
-    HIP_CHECK(hipMemcpyAsync(htimes.data(), stm, n * 8,
-                             hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (u64 i = 0; i < n;) {
-      u64 j = i;
-      while (j < n && htimes[j] == htimes[i]) j++;
-      slices.push_back({i, j});
-      i = j;
-    }
-  }
-  // output buffer: capacity 2 * n corrections max (each input row can
-  // change at most one key per slice; 2 rows per changed key per slice)
-  u64 cap_out = 2 * n + 16;
-  u64 *pk = dnew<u64>(ctx, cap_out * okw);
-  u8 *pv = (u8 *)dmalloc(ctx, cap_out * ovb);
-  u64 *pt = dnew<u64>(ctx, cap_out);
-  i64 *pd = dnew<i64>(ctx, cap_out);
-  unsigned long long *ocount = (unsigned long long *)S.get(8);
-  fill_u64(ctx, (u64 *)ocount, 1, 0);
-  u32 *flags = (u32 *)S.get(n * 4);
-  u32 *gid = (u32 *)S.get(n * 4);
+  SortedCols s = sort_gather(ctx, d.keys, kw, d.vals, vb, d.times, d.diffs, n);
+  std::vector<TimeSlice> slices = time_slices(ctx, s.times, n, lower, upper);
+  // capacity 2 * n corrections max (each input row can change at most one
+  // key per slice; 2 rows per changed key per slice)
+  CorrBuf cb = corr_alloc(ctx, 2 * n + 16, okw, ovb);
   // DISTINCT aggregates: the (key, datum) stream of each, sorted by
   // (time, key, datum). NULL datums stay as neutral rows, so the sorted
-  // times equal stm and the slices below cut both streams alike.
+  // times equal s.times and the slices below cut both streams alike.
+  u32 kw2 = kw + 1;  // pair tables' combined key: [key words][datum]
   u64 *psk[MZ_GPU_MAX_AGGS];
   i64 *psd[MZ_GPU_MAX_AGGS];
   for (u32 j = 0; j < op->n_dist; j++) {
@@ -5221,219 +5346,54 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
     hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0,
                        ctx->stream, pdf, pperm, psd[j], n);
   }
-  for (auto [lo, hi] : slices) {
+  for (auto [lo, hi, t] : slices) {
     u64 m = hi - lo;
     // Pair stage: fold the slice into each pair table and leave one
     // presence delta per (key, datum) group for the key stage, which runs
     // in a later launch than every pair apply it reads.
     PairViews pvs{};
     for (u32 j = 0; j < op->n_dist; j++) {
+      const KeyedTable &P = op->ptbl[j];
       const u64 *pck = psk[j] + lo * kw2;
-      u32 *pflags = (u32 *)S.get(m * 4);
-      u32 *pgid = (u32 *)S.get(m * 4);
-      u32 *pstarts = (u32 *)S.get(m * 4);
-      hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
-                         ctx->stream, pck, kw2, stm + lo, pflags, m);
-      inclusive_scan_u32(ctx, pflags, pgid, m);
-      hipLaunchKernelGGL(k_group_starts, dim3(ngrid(m)), dim3(BLK), 0,
-                         ctx->stream, pflags, pgid, pstarts, m);
-      u32 *pfound = (u32 *)S.get(m * 4);
-      u32 *pmiss = (u32 *)S.get(m * 4);
-      hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(m)), dim3(BLK), 0,
-                         ctx->stream, pck, kw2, pstarts, 0, pgid, m,
-                         op->pst[j], pfound, pmiss);
-      u32 *pmisspos = (u32 *)S.get((m + 1) * 4);
-      exclusive_scan_u32_ns(ctx, pmiss, pmisspos, m);
-      hipLaunchKernelGGL(k_red_insert, dim3(ngrid(m)), dim3(BLK), 0,
-                         ctx->stream, pck, kw2, pstarts, 0, pgid, m, pmiss,
-                         pmisspos, 0, op->d_pnrows + j, op->d_err,
-                         op->pst[j]);
+      Groups pg = group_sorted(ctx, pck, kw2, s.times + lo, m);
+      Upsert pu = kt_upsert(ctx, P, pck, pg, m);
       int *pdelta = (int *)S.get(m * 4);
       hipLaunchKernelGGL(k_pair_apply, dim3(ngrid(m)), dim3(BLK), 0,
-                         ctx->stream, psd[j] + lo, pstarts, pgid, m,
-                         op->pst[j], pfound, pmiss, pmisspos,
-                         op->d_pnrows + j, pdelta);
-      hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
-                         op->d_pnrows + j, pmisspos, pgid, m);
-      pvs.v[op->dist_agg[j]] = PairView{pck, pstarts, pgid, pdelta};
+                         ctx->stream, psd[j] + lo, pg.starts, pg.gid, m, P.st,
+                         pu.found, pu.miss, pu.misspos, P.d_nrows, pdelta);
+      kt_commit(ctx, P, pu, pg, m);
+      pvs.v[op->dist_agg[j]] = PairView{pck, pg.starts, pg.gid, pdelta};
     }
-    // key-group starts within the slice (group count stays on device)
-    hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, stm + lo, flags, m);
-    inclusive_scan_u32(ctx, flags, gid, m);
-    u32 *starts = (u32 *)S.get(m * 4);
-    hipLaunchKernelGGL(k_group_starts, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, flags, gid, starts, m);
-    if (getenv("MZ_DBG_SORT")) {
-      // diagnostic: recompute flags/gid on host from the gathered columns
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      std::vector<u64> hsk(m * kw), hstm(m);
-      std::vector<u32> hflags(m), hgid(m);
-      HIP_CHECK(hipMemcpy(hsk.data(), sk + lo * kw, m * kw * 8,
-                          hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(hstm.data(), stm + lo, m * 8,
-                          hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(hflags.data(), flags, m * 4,
-                          hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(hgid.data(), gid, m * 4, hipMemcpyDeviceToHost));
-      u64 flag_bad = ~0ull, gid_bad = ~0ull;
-      u32 run = 0;
-      for (u64 i = 0; i < m; i++) {
-        u32 want = 1;
-        if (i) {
-          bool neq = hstm[i] != hstm[i - 1];
-          for (u32 w = 0; w < kw && !neq; w++)
-            neq |= hsk[i * kw + w] != hsk[(i - 1) * kw + w];
-          want = neq ? 1 : 0;
-        }
-        if (hflags[i] != want && flag_bad == ~0ull) flag_bad = i;
-        run += want;  // recomputed scan uses *want*, so gid_bad isolates
-        if (hgid[i] != run && gid_bad == ~0ull) gid_bad = i;  // the scan
-      }
-      fprintf(stderr, "[dbg_grp] m=%llu flag_bad=%lld gid_bad=%lld "
-              "G_dev=%u G_host=%u sorted_gather_key0=%lld\n",
-              (unsigned long long)m, (long long)flag_bad, (long long)gid_bad,
-              hgid[m - 1], run, (long long)hsk[0]);
-      if (flag_bad != ~0ull || gid_bad != ~0ull) {
-        u64 b0 = std::min(flag_bad, gid_bad);
-        for (u64 i = (b0 > 2 ? b0 - 2 : 0); i < std::min<u64>(m, b0 + 3);
-             i++)
-          fprintf(stderr, "[dbg_grp]  i=%llu flag=%u gid=%u key=%lld "
-                  "t=%llu\n", (unsigned long long)i, hflags[i], hgid[i],
-                  (long long)hsk[i * kw], (unsigned long long)hstm[i]);
-      }
-      fflush(stderr);
-    }
-    if (getenv("MZ_DBG_TBL")) {
-      // two views of the slot the first group's key probes: kernel-read
-      // (through L2) vs hipMemcpy (DMA) — distinguishes "memory truly
-      // not 0xFF" from "kernel sees stale cache"
-      u64 *dslot = (u64 *)S.get((kw + 2) * 8);
-      hipLaunchKernelGGL(k_dbg_read_slot, dim3(1), dim3(1), 0, ctx->stream,
-                         op->st.hash, op->st.slots, sk + lo * kw, kw, dslot);
-      std::vector<u64> kview(kw + 2), key0(kw);
-      HIP_CHECK(hipMemcpy(kview.data(), dslot, (kw + 2) * 8,
-                          hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(key0.data(), sk + lo * kw, kw * 8,
-                          hipMemcpyDeviceToHost));
-      u64 h = route_hash(key0.data(), kw) & (op->st.slots - 1);
-      std::vector<u64> mview(kw + 1);
-      HIP_CHECK(hipMemcpy(mview.data(), op->st.hash + h * (kw + 1),
-                          (kw + 1) * 8, hipMemcpyDeviceToHost));
-      fprintf(stderr, "[dbg_tbl] key0=%lld h=%llu kernel_view=",
-              (long long)key0[0], (unsigned long long)kview[kw + 1]);
-      for (u32 w = 0; w < kw + 1; w++)
-        fprintf(stderr, "%llx,", (unsigned long long)kview[w]);
-      fprintf(stderr, " memcpy_view=");
-      for (u32 w = 0; w < kw + 1; w++)
-        fprintf(stderr, "%llx,", (unsigned long long)mview[w]);
-      fprintf(stderr, "\n");
-      fflush(stderr);
-    }
-    // Phase A: lookup; Phase B: insert misses (separate launches for
-    // coherence — see RedState docs); Phase C: apply + emit; bump counter.
-    u32 *found = (u32 *)S.get(m * 4);
-    u32 *miss = (u32 *)S.get(m * 4);
-    hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, starts, 0, gid, m,
-                       op->st, found, miss);
-    u32 *misspos = (u32 *)S.get((m + 1) * 4);
-    exclusive_scan_u32_ns(ctx, miss, misspos, m);
-    hipLaunchKernelGGL(k_red_insert, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, starts, 0, gid, m,
-                       miss, misspos, 0, op->d_nrows, op->d_err, op->st);
+    // Key stage
+    const u64 *sk = s.keys + lo * kw;
+    Groups g = group_sorted(ctx, sk, kw, s.times + lo, m);
+    Upsert up = kt_upsert(ctx, op->tbl, sk, g, m);
     if (op->n_dist)
       hipLaunchKernelGGL(k_reduce_apply_distinct, dim3(ngrid(m)), dim3(BLK),
-                         0, ctx->stream, sk + lo * kw, sv + lo * vb, kw, vb,
-                         sd + lo, starts, gid, m,
-                         htimes[htimes.size() == 1 ? 0 : lo], op->st, found,
-                         miss, misspos, op->d_nrows, op->spec, pvs, pk, pv,
-                         pt, pd, ocount);
+                         0, ctx->stream, sk, s.vals + lo * vb, kw, vb,
+                         s.diffs + lo, g.starts, g.gid, m, t, op->tbl.st,
+                         up.found, up.miss, up.misspos, op->tbl.d_nrows,
+                         op->spec, pvs, cb.pk, cb.pv, cb.pt, cb.pd,
+                         cb.ocount);
     else
       hipLaunchKernelGGL(k_reduce_apply, dim3(ngrid(m)), dim3(BLK), 0,
-                         ctx->stream, sk + lo * kw, sv + lo * vb, kw, vb,
-                         sd + lo, starts, 0, gid, m,
-                         htimes[htimes.size() == 1 ? 0 : lo], op->st, found,
-                         miss, misspos, 0, op->d_nrows, op->spec, pk, pv, pt,
-                         pd, ocount);
-    hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
-                       op->d_nrows, misspos, gid, m);
-    if (getenv("MZ_DBG_SORT")) {
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      std::vector<u32> hgid(m), hstarts(m), hfound(m), hmiss(m);
-      std::vector<u64> hsk(m * kw);
-      HIP_CHECK(hipMemcpy(hgid.data(), gid, m * 4, hipMemcpyDeviceToHost));
-      u64 G = hgid[m - 1];
-      if (G > m) {
-        fprintf(stderr, "[dbg_red] GARBAGE G=%llu > m=%llu\n",
-                (unsigned long long)G, (unsigned long long)m);
-        fflush(stderr);
-        continue;
-      }
-      hstarts.resize(G ? G : 1);
-      hfound.resize(G ? G : 1);
-      hmiss.resize(G ? G : 1);
-      HIP_CHECK(hipMemcpy(hstarts.data(), starts, G * 4,
-                          hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(hfound.data(), found, G * 4,
-                          hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(hmiss.data(), miss, G * 4, hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(hsk.data(), sk + lo * kw, m * kw * 8,
-                          hipMemcpyDeviceToHost));
-      // groups must carry distinct keys (input sorted by key within slice)
-      bool dup = false;
-      for (u64 g1 = 0; g1 + 1 < G && !dup; g1++)
-        for (u64 g2 = g1 + 1; g2 < G && !dup; g2++) {
-          bool eq = true;
-          for (u32 w = 0; w < kw; w++)
-            eq &= hsk[(u64)hstarts[g1] * kw + w] ==
-                  hsk[(u64)hstarts[g2] * kw + w];
-          dup = eq;
-        }
-      u64 nmiss = 0, nfound_bad = 0;
-      for (u64 g1 = 0; g1 < G; g1++) nmiss += hmiss[g1];
-      for (u64 g1 = 0; g1 < G; g1++)
-        if (!hmiss[g1] && hfound[g1] == ~0u) nfound_bad++;
-      unsigned long long hoc = 0;
-      HIP_CHECK(hipMemcpy(&hoc, ocount, 8, hipMemcpyDeviceToHost));
-      fprintf(stderr, "[dbg_red] slice m=%llu G=%llu dup_groups=%d "
-              "misses=%llu found_bad=%llu emitted=%llu\n",
-              (unsigned long long)m, (unsigned long long)G, (int)dup,
-              (unsigned long long)nmiss, (unsigned long long)nfound_bad,
-              hoc);
-      fflush(stderr);
-    }
+                         ctx->stream, sk, s.vals + lo * vb, kw, vb,
+                         s.diffs + lo, g.starts, g.gid, m, t, op->tbl.st,
+                         up.found, up.miss, up.misspos, op->tbl.d_nrows,
+                         op->spec, cb.pk, cb.pv, cb.pt, cb.pd, cb.ocount);
+    kt_commit(ctx, op->tbl, up, g, m);
   }
-  // consolidate the actual emitted corrections (one count readback —
-  // sorting the 2n-capacity zero-padded buffer dominated this path)
-  u64 *stage = (u64 *)ctx->pin;
-  HIP_CHECK(hipMemcpyAsync(stage, ocount, 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(stage + 1, op->d_err, 8,
-                           hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(stage + 2, op->d_nrows, 8,
-                           hipMemcpyDeviceToHost, ctx->stream));
-  if (op->n_dist)  // the pair tables' mirrors ride the same readback
-    HIP_CHECK(hipMemcpyAsync(stage + 3, op->d_pnrows, 8 * op->n_dist,
-                             hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  u64 emitted = stage[0], errflag = stage[1];
-  op->n_rows = stage[2];
-  for (u32 j = 0; j < op->n_dist; j++) op->p_nrows[j] = stage[3 + j];
-  DevUpdates pin{pk, pv, pt, pd, (u64)emitted};
-  u64 *ok;
-  u8 *ov;
-  u64 *ot;
-  i64 *od;
-  u64 Mc;
-  consolidate_dev(ctx, okw, ovb, pin, &ok, &ov, &ot, &od, &Mc);
-  for (void *p : {(void *)pk, (void *)pv, (void *)pt, (void *)pd})
-    dfree(ctx, (p));
+  // count + the whole counter block [key rows][err][pair rows] at once
+  const u64 *h = corr_read(ctx, cb, op->d_ctr, 2 + op->n_dist);
+  u64 emitted = h[0], errflag = h[2];
+  op->tbl.n_rows = h[1];
+  for (u32 j = 0; j < op->n_dist; j++) op->ptbl[j].n_rows = h[3 + j];
+  mz_gpu_out *o = corr_finish(ctx, cb, emitted, errflag != 0);
   if (errflag) {
     ctx->err = "reduce state capacity exceeded";
     return -1;
   }
-  *out = make_out(ok, ov, ot, od, Mc, okw, ovb);
+  *out = o;
   return 0;
 }
 
@@ -5447,28 +5407,14 @@ mz_gpu_thr *mz_gpu_threshold_create(mz_gpu_ctx *c, const mz_gpu_schema *s) {
   mz_gpu_thr *r = new mz_gpu_thr();
   r->s = *s;
   r->kw2 = s->key_words + (s->val_bytes + 7) / 8;
-  u64 cap = 1ull << 21;  // 2M (key,val) pairs default; grows on demand
-  if (const char *e = getenv("MZ_GPU_THR_CAP")) cap = (u64)atoll(e);
-  r->capacity = cap;
-  u64 slots = 2 * cap;
-  r->st.hash = dnew<u64>(ctx, slots * (r->kw2 + 1));
-  r->st.slots = slots;
-  r->st.stride_w = r->kw2 + 1;
-  r->st.rows = dnew<u64>(ctx, cap * r->st.stride_w);
-  r->st.capacity = cap;
-  r->d_nrows = dnew<u64>(ctx, 1);
-  r->d_err = dnew<u64>(ctx, 1);
-  fill_u64(ctx, r->d_nrows, 1, 0);
-  fill_u64(ctx, r->d_err, 1, 0);
-  fill_u64(ctx, r->st.hash, slots * (r->kw2 + 1), ~0ull);
+  // 2M (key,val) pairs default; grows on demand; payload = the net count
+  kt_create(ctx, r->tbl, r->kw2, 1, kt_env_cap("MZ_GPU_THR_CAP", 1ull << 21));
   return r;
 }
 
 void mz_gpu_threshold_drop(mz_gpu_ctx *c, mz_gpu_thr *r) {
   Ctx *ctx = &c->impl;
-  for (void *p : {(void *)r->st.hash, (void *)r->st.rows,
-                  (void *)r->d_nrows, (void *)r->d_err})
-    dfree(ctx, p);
+  kt_free(ctx, r->tbl);
   delete r;
 }
 
@@ -5480,107 +5426,41 @@ int mz_gpu_threshold_push(mz_gpu_ctx *c, mz_gpu_thr *op,
   u32 kw = op->s.key_words, vb = op->s.val_bytes, kw2 = op->kw2;
   DevUpdates d = stage_updates(ctx, u, kw, vb);
   u64 n = d.n;
-  if (op->n_rows + n > op->capacity) {
-    red_compact_grow(ctx, op->st, op->d_nrows, op->n_rows, n, kw2, kw2);
-    op->capacity = op->st.capacity;
-  }
+  kt_reserve(ctx, op->tbl, n);
   if (n == 0) {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                    dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, kw, vb);
+    *out = empty_out(ctx, kw, vb);
     return 0;
   }
   u64 *ck = (u64 *)S.get(n * kw2 * 8);
   hipLaunchKernelGGL(k_pack_combined, dim3(ngrid(n)), dim3(BLK), 0,
                      ctx->stream, d.keys, kw, vb ? d.vals : nullptr, vb, n,
                      ck, kw2);
-  // sort by (time, combined key)
-  u32 *perm = (u32 *)S.get(n * 4);
-  sort_updates(ctx, ck, kw2, nullptr, 0, d.times, n, perm, true);
-  u64 *sk = (u64 *)S.get(n * kw2 * 8);
-  u64 *stm = (u64 *)S.get(n * 8);
-  i64 *sd = (i64 *)S.get(n * 8);
-  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
-                     ctx->stream, ck, kw2, perm, sk, n);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.times, perm, stm, n);
-  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.diffs, perm, sd, n);
-  std::vector<u64> htimes;
-  std::vector<std::pair<u64, u64>> slices;
-  if (u->upper <= u->lower + 1) {
-    htimes.assign(1, u->lower);
-    slices.push_back({0, n});
-  } else {
-    htimes.resize(n);
-    HIP_CHECK(hipMemcpyAsync(htimes.data(), stm, n * 8,
-                             hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (u64 i = 0; i < n;) {
-      u64 j = i;
-      while (j < n && htimes[j] == htimes[i]) j++;
-      slices.push_back({i, j});
-      i = j;
-    }
-  }
-  u64 cap_out = n + 16;  // ≤1 correction per group per slice
-  u64 *pk = dnew<u64>(ctx, cap_out * kw);
-  u8 *pv = (u8 *)dmalloc(ctx, std::max<u64>(cap_out * vb, 1));
-  u64 *pt = dnew<u64>(ctx, cap_out);
-  i64 *pd = dnew<i64>(ctx, cap_out);
-  unsigned long long *ocount = (unsigned long long *)S.get(8);
-  fill_u64(ctx, (u64 *)ocount, 1, 0);
-  u32 *flags = (u32 *)S.get(n * 4);
-  u32 *gid = (u32 *)S.get(n * 4);
-  for (auto [lo, hi] : slices) {
+  // sorted by (time, combined key)
+  SortedCols s = sort_gather(ctx, ck, kw2, nullptr, 0, d.times, d.diffs, n);
+  std::vector<TimeSlice> slices =
+      time_slices(ctx, s.times, n, u->lower, u->upper);
+  CorrBuf cb = corr_alloc(ctx, n + 16, kw, vb);  // ≤1 row per group per slice
+  for (auto [lo, hi, t] : slices) {
     u64 m = hi - lo;
-    hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw2, kw2, stm + lo, flags, m);
-    inclusive_scan_u32(ctx, flags, gid, m);
-    u32 *starts = (u32 *)S.get(m * 4);
-    hipLaunchKernelGGL(k_group_starts, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, flags, gid, starts, m);
-    u32 *found = (u32 *)S.get(m * 4);
-    u32 *miss = (u32 *)S.get(m * 4);
-    hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw2, kw2, starts, 0, gid, m,
-                       op->st, found, miss);
-    u32 *misspos = (u32 *)S.get((m + 1) * 4);
-    exclusive_scan_u32_ns(ctx, miss, misspos, m);
-    hipLaunchKernelGGL(k_red_insert, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw2, kw2, starts, 0, gid, m,
-                       miss, misspos, 0, op->d_nrows, op->d_err, op->st);
+    const u64 *sk = s.keys + lo * kw2;
+    Groups g = group_sorted(ctx, sk, kw2, s.times + lo, m);
+    Upsert up = kt_upsert(ctx, op->tbl, sk, g, m);
     hipLaunchKernelGGL(k_threshold_apply, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw2, kw2, sd + lo, starts, gid,
-                       m, htimes[htimes.size() == 1 ? 0 : lo], op->st, found,
-                       miss, misspos, op->d_nrows, kw, vb, pk, pv, pt, pd,
-                       ocount);
-    hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
-                       op->d_nrows, misspos, gid, m);
+                       ctx->stream, sk, kw2, s.diffs + lo, g.starts, g.gid, m,
+                       t, op->tbl.st, up.found, up.miss, up.misspos,
+                       op->tbl.d_nrows, kw, vb, cb.pk, cb.pv, cb.pt, cb.pd,
+                       cb.ocount);
+    kt_commit(ctx, op->tbl, up, g, m);
   }
-  u64 *stage = (u64 *)ctx->pin;
-  HIP_CHECK(hipMemcpyAsync(stage, ocount, 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(stage + 1, op->d_err, 8,
-                           hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(stage + 2, op->d_nrows, 8,
-                           hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  u64 emitted = stage[0], errflag = stage[1];
-  op->n_rows = stage[2];
-  DevUpdates pin{pk, pv, pt, pd, (u64)emitted};
-  u64 *ok;
-  u8 *ov;
-  u64 *ot;
-  i64 *od;
-  u64 Mc;
-  consolidate_dev(ctx, kw, vb, pin, &ok, &ov, &ot, &od, &Mc);
-  for (void *p : {(void *)pk, (void *)pv, (void *)pt, (void *)pd})
-    dfree(ctx, p);
+  const u64 *h = corr_read(ctx, cb, op->tbl.d_nrows, 2);  // [rows][err]
+  u64 emitted = h[0], errflag = h[2];
+  op->tbl.n_rows = h[1];
+  mz_gpu_out *o = corr_finish(ctx, cb, emitted, errflag != 0);
   if (errflag) {
     ctx->err = "threshold state capacity exceeded";
     return -1;
   }
-  *out = make_out(ok, ov, ot, od, Mc, kw, vb);
+  *out = o;
   return 0;
 }
 
@@ -5655,19 +5535,12 @@ static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
                        ctx->stream, vals, vb, perm, sv2, n);
   hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0,
                      ctx->stream, diffs, perm, sd2, n);
-  u32 *flags = (u32 *)S.get(n * 4);
-  u32 *gid = (u32 *)S.get(n * 4);
   // eval rows all carry time t (the peek probe's join time)
-  hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(n)), dim3(BLK), 0,
-                     ctx->stream, sk2, kw, (const u64 *)pe->times, flags, n);
-  inclusive_scan_u32(ctx, flags, gid, n);
-  u32 *starts = (u32 *)S.get(n * 4);
-  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(n)), dim3(BLK), 0,
-                     ctx->stream, flags, gid, starts, n);
+  Groups g = group_sorted(ctx, sk2, kw, (const u64 *)pe->times, n);
   u64 *pre = (u64 *)S.get(n * 8);
   inclusive_scan_u64(ctx, (const u64 *)sd2, pre, n);
   hipLaunchKernelGGL(k_topk_kept, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     sk2, kw, sv2, vb, sd2, pre, starts, gid, n,
+                     sk2, kw, sv2, vb, sd2, pre, g.starts, g.gid, n,
                      op->spec.offset, (i64)op->spec.limit, t, sign, pk, pv,
                      pt, pd, ocount);
 }
@@ -5696,8 +5569,7 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
   DevUpdates d = stage_updates(ctx, u, kw, vb);
   u64 n = d.n;
   if (n == 0) {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                    dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, kw, vb);
+    *out = empty_out(ctx, kw, vb);
     return 0;
   }
   // Owned sorted columns: they outlive spine merges' scratch resets.
@@ -5716,40 +5588,17 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
                      d.times, perm, stm, n);
   hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
                      d.diffs, perm, sd, n);
-  std::vector<u64> htimes;
-  std::vector<std::pair<u64, u64>> slices;
-  if (u->upper <= u->lower + 1) {
-    htimes.assign(1, u->lower);
-    slices.push_back({0, n});
-  } else {
-    htimes.resize(n);
-    HIP_CHECK(hipMemcpyAsync(htimes.data(), stm, n * 8,
-                             hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (u64 i = 0; i < n;) {
-      u64 j = i;
-      while (j < n && htimes[j] == htimes[i]) j++;
-      slices.push_back({i, j});
-      i = j;
-    }
-  }
+  std::vector<TimeSlice> slices =
+      time_slices(ctx, stm, n, u->lower, u->upper);
   std::vector<std::array<void *, 4>> segs;
   std::vector<u64> segn;
   int rc = 0;
-  for (auto [lo, hi] : slices) {
+  for (auto [lo, hi, t] : slices) {
     u64 m = hi - lo;
-    u64 t = htimes[htimes.size() == 1 ? 0 : lo];
     auto &S = (*ctx->scr);
-    u32 *flags = (u32 *)S.get(m * 4);
-    u32 *gid = (u32 *)S.get(m * 4);
-    hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, stm + lo, flags, m);
-    inclusive_scan_u32(ctx, flags, gid, m);
-    u32 *starts = (u32 *)S.get(m * 4);
-    hipLaunchKernelGGL(k_group_starts, dim3(ngrid(m)), dim3(BLK), 0,
-                       ctx->stream, flags, gid, starts, m);
+    Groups g = group_sorted(ctx, sk + lo * kw, kw, stm + lo, m);
     u32 G32 = 0;
-    HIP_CHECK(hipMemcpyAsync(&G32, gid + (m - 1), 4, hipMemcpyDeviceToHost,
+    HIP_CHECK(hipMemcpyAsync(&G32, g.gid + (m - 1), 4, hipMemcpyDeviceToHost,
                              ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     u64 G = G32;
@@ -5757,7 +5606,8 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
     u64 *gt = dnew<u64>(ctx, G);
     i64 *gd = dnew<i64>(ctx, G);
     hipLaunchKernelGGL(k_gather_group_keys, dim3(ngrid(G)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, starts, gid, m, dg);
+                       ctx->stream, sk + lo * kw, kw, g.starts, g.gid, m,
+                       dg);
     hipLaunchKernelGGL(k_fill_u64, dim3(ngrid(G)), dim3(BLK), 0,
                        ctx->stream, gt, G, t);
     hipLaunchKernelGGL(k_fill_i64, dim3(ngrid(G)), dim3(BLK), 0,
@@ -5812,9 +5662,7 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
       HIP_CHECK(hipMemcpyAsync(&errflag, op->d_err, 8,
                                hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (!errflag)
-        *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                        dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, kw, vb);
+      if (!errflag) *out = empty_out(ctx, kw, vb);
     } else {
       u64 *ck2 = dnew<u64>(ctx, total * kw);
       u8 *cv2 = (u8 *)dmalloc(ctx, std::max<u64>(total * vb, 1));
@@ -5972,8 +5820,7 @@ int mz_gpu_map(mz_gpu_ctx *c, const mz_gpu_schema *in,
   DevUpdates d = stage_updates(ctx, u, kw, vb);
   u64 n = d.n;
   if (n == 0) {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                    dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, okw, ovb);
+    *out = empty_out(ctx, okw, ovb);
     return 0;
   }
   u32 *flags = (u32 *)S.get(n * 4);
@@ -6000,8 +5847,7 @@ struct mz_gpu_minmax {
   int is_max;
   std::vector<u32> buckets;
   std::vector<mz_gpu_arr> levels;
-  std::vector<RedState> states;
-  std::vector<u64> n_rows;
+  std::vector<KeyedTable> states;  // host-counted; capacity fixed at create
 };
 
 mz_gpu_minmax *mz_gpu_minmax_create(mz_gpu_ctx *c, const mz_gpu_schema *in,
@@ -6014,19 +5860,11 @@ mz_gpu_minmax *mz_gpu_minmax_create(mz_gpu_ctx *c, const mz_gpu_schema *in,
   op->buckets.assign(buckets, buckets + n_levels);
   op->levels.resize(n_levels);
   op->states.resize(n_levels);
-  op->n_rows.assign(n_levels, 0);
   u32 kw2 = op->kw + 1;
   for (u32 l = 0; l < n_levels; l++) {
     op->levels[l].schema = {kw2, 8};
-    RedState &st = op->states[l];
-    u64 cap = 1ull << 21;
-    u64 slots = 2 * cap;
-    st.hash = dnew<u64>(ctx, slots * (kw2 + 1));
-    st.slots = slots;
-    st.stride_w = kw2 + 2;  // [key][exists][value]
-    st.rows = dnew<u64>(ctx, cap * st.stride_w);
-    st.capacity = cap;
-    fill_u64(ctx, st.hash, slots * (kw2 + 1), ~0ull);
+    // rows [key][exists][value]
+    kt_create_at(ctx, op->states[l], kw2, 2, 1ull << 21, nullptr, nullptr);
   }
   return op;
 }
@@ -6078,7 +5916,9 @@ static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
       break;
     }
     // 3-phase state upsert over the changed groups (batch keys = the
-    // sorted distinct changed keys)
+    // sorted distinct changed keys), host-counted: the miss total is read
+    // back, so the capacity check is exact and fails the push
+    KeyedTable &T = op->states[l];
     u32 *gstart = (u32 *)S.get(G * 4);
     hipLaunchKernelGGL(k_iota, dim3(ngrid(G)), dim3(BLK), 0, ctx->stream,
                        gstart, G);
@@ -6086,10 +5926,10 @@ static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
     u32 *miss = (u32 *)S.get(G * 4);
     hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(G)), dim3(BLK), 0,
                        ctx->stream, nb->keys, kw2, gstart, G,
-                       (const u32 *)nullptr, 0, op->states[l], found, miss);
+                       (const u32 *)nullptr, 0, T.st, found, miss);
     u32 *misspos = (u32 *)S.get((G + 1) * 4);
     u64 Mn = exclusive_scan_u32(ctx, miss, misspos, G);
-    if (op->n_rows[l] + Mn > op->states[l].capacity) {
+    if (T.n_rows + Mn > T.st.capacity) {
       ctx->err = "minmax state capacity exceeded";
       return -1;
     }
@@ -6097,8 +5937,8 @@ static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
       hipLaunchKernelGGL(k_red_insert, dim3(ngrid(G)), dim3(BLK), 0,
                          ctx->stream, nb->keys, kw2, gstart, G,
                          (const u32 *)nullptr, 0, miss, misspos,
-                         op->n_rows[l], (const u64 *)nullptr,
-                         (u64 *)nullptr, op->states[l]);
+                         T.n_rows, (const u64 *)nullptr, (u64 *)nullptr,
+                         T.st);
     // output buffer for this level's corrections
     u32 out_kw = (l + 1 < L) ? kw2 : kw;
     u32 bnext = (l + 1 < L) ? op->buckets[l + 1] : 1;
@@ -6120,9 +5960,9 @@ static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
       }
     hipLaunchKernelGGL(k_minmax_apply, dim3(ngrid(G)), dim3(BLK), 0,
                        ctx->stream, nb->keys, G, kw2, bl, op->is_max,
-                       op->states[l], found, miss, misspos, op->n_rows[l],
+                       T.st, found, miss, misspos, T.n_rows,
                        out_kw, bnext, t, pk, pv, pt, pd, ocount);
-    op->n_rows[l] += Mn;
+    T.n_rows += Mn;
     unsigned long long M;
     HIP_CHECK(hipMemcpyAsync(&M, ocount, 8, hipMemcpyDeviceToHost,
                              ctx->stream));
@@ -6156,10 +5996,7 @@ void mz_gpu_minmax_drop(mz_gpu_ctx *c, mz_gpu_minmax *op) {
     for (auto &b : lvl.batches) free_batch(ctx, b);
     lvl.batches.clear();
   }
-  for (auto &st : op->states) {
-    dfree(ctx, st.hash);
-    dfree(ctx, st.rows);
-  }
+  for (auto &T : op->states) kt_free(ctx, T);
   delete op;
 }
 
@@ -6170,10 +6007,8 @@ struct mz_gpu_collation {
   mz_gpu_red *red = nullptr;        // part 0 (null: no accumulable aggs)
   std::vector<mz_gpu_minmax *> mms;  // one part per MIN/MAX aggregate
   std::vector<mz_gpu_aggregate> mm_aggs;
-  RedState st;                      // resident stitch state
-  u64 n_rows = 0;                   // host mirror of *d_nrows
-  u64 *d_nrows = nullptr;
-  u64 *d_err = nullptr;             // [0] capacity, [1] missing part
+  KeyedTable tbl;  // resident stitch state; d_err[0] capacity,
+                   // d_err[1] missing part
   // The parts run on this arena: the main arena holds the staged input
   // and the projected columns across all parts and is reset once per
   // push, while a part may reset its arena freely (a bucket level's spine
@@ -6196,9 +6031,7 @@ struct ScrGuard {
 static void collation_free(mz_gpu_ctx *c, mz_gpu_collation *op) {
   Ctx *ctx = &c->impl;
   for (mz_gpu_minmax *m : op->mms) mz_gpu_minmax_drop(c, m);
-  for (void *p : {(void *)op->st.hash, (void *)op->st.rows,
-                  (void *)op->d_nrows, (void *)op->d_err})
-    dfree(ctx, p);
+  kt_free(ctx, op->tbl);
   (void)hipStreamSynchronize(ctx->stream);
   op->sub.destroy();
   delete op;
@@ -6293,22 +6126,11 @@ mz_gpu_collation *mz_gpu_collation_create(mz_gpu_ctx *c,
     op->mms.push_back(mz_gpu_minmax_create(
         c, &mm_in, op->mm_aggs[j].func == MZ_AGG_MAX_I64, spec->buckets,
         spec->n_levels));
-  u64 cap = 1ull << 20;  // grows on demand; env override for tests/tuning
-  if (const char *e = getenv("MZ_GPU_COL_CAP")) cap = (u64)atoll(e);
-  u64 p2 = 16;  // the hash masks with slots - 1: keep a power of two
-  while (p2 < cap) p2 *= 2;
-  cap = p2;
-  RedState &st = op->st;
-  st.slots = 2 * cap;
-  st.capacity = cap;
-  st.stride_w = kw + 1 + L.PW;
-  st.hash = dnew<u64>(ctx, st.slots * (kw + 1));
-  st.rows = dnew<u64>(ctx, cap * st.stride_w);
-  op->d_nrows = dnew<u64>(ctx, 1);
-  op->d_err = dnew<u64>(ctx, 2);
-  fill_u64(ctx, op->d_nrows, 1, 0);
-  fill_u64(ctx, op->d_err, 2, 0);
-  fill_u64(ctx, st.hash, st.slots * (kw + 1), ~0ull);
+  // 1M keys default; grows on demand; env override for tests/tuning
+  u64 want = kt_env_cap("MZ_GPU_COL_CAP", 1ull << 20);
+  u64 cap = 16;  // the hash masks with slots - 1: keep a power of two
+  while (cap < want) cap *= 2;
+  kt_create(ctx, op->tbl, kw, 1 + L.PW, cap, /*n_err=*/2);
   ctx->cols.push_back(op);
   return op;
 }
@@ -6339,12 +6161,10 @@ int mz_gpu_collation_push(mz_gpu_ctx *c, mz_gpu_collation *op,
   u64 t = u->lower;
   DevUpdates d = stage_updates(ctx, u, kw, vb);
   u64 n = d.n;
-  auto empty_out = [&]() {
-    *out = make_out(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                    dnew<u64>(ctx, 1), dnew<i64>(ctx, 1), 0, kw, ovb);
+  if (n == 0) {
+    *out = empty_out(ctx, kw, ovb);
     return 0;
-  };
-  if (n == 0) return empty_out();
+  }
   // ---- parts: each reduction type on its own, over the same input
   std::vector<mz_gpu_out *> pouts(L.n_parts, nullptr);
   auto release_parts = [&]() {
@@ -6378,13 +6198,12 @@ int mz_gpu_collation_push(mz_gpu_ctx *c, mz_gpu_collation *op,
   for (mz_gpu_out *o : pouts) R += o->n;
   if (R == 0) {
     release_parts();
-    return empty_out();
+    *out = empty_out(ctx, kw, ovb);
+    return 0;
   }
   MZ_PROF(ctx, "collation_stitch");
   // every changed key has a correction row in some part, and an input row
-  if (op->n_rows + std::min(R, n) > op->st.capacity)
-    red_compact_grow(ctx, op->st, op->d_nrows, op->n_rows, std::min(R, n),
-                     kw, kw);
+  kt_reserve(ctx, op->tbl, std::min(R, n));
   // ---- tagged stream (key, part, diff, val padded), sorted by key
   u64 *tk = (u64 *)S.get(R * kw * 8);
   u64 *tv = (u64 *)S.get(R * L.W * 8);
@@ -6405,67 +6224,29 @@ int mz_gpu_collation_push(mz_gpu_ctx *c, mz_gpu_collation *op,
   u64 *sk = (u64 *)S.get(R * kw * 8);
   hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(R)), dim3(BLK), 0,
                      ctx->stream, tk, kw, perm, sk, R);
-  u32 *flags = (u32 *)S.get(R * 4);
-  u32 *gid = (u32 *)S.get(R * 4);
-  u32 *starts = (u32 *)S.get(R * 4);
-  hipLaunchKernelGGL(k_key_flags_sorted, dim3(ngrid(R)), dim3(BLK), 0,
-                     ctx->stream, sk, kw, tt, flags, R);
-  inclusive_scan_u32(ctx, flags, gid, R);
-  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(R)), dim3(BLK), 0,
-                     ctx->stream, flags, gid, starts, R);
   // ---- stitch upsert: lookup, insert, apply as three launches
-  u32 *found = (u32 *)S.get(R * 4);
-  u32 *miss = (u32 *)S.get(R * 4);
-  u32 *misspos = (u32 *)S.get((R + 1) * 4);
-  hipLaunchKernelGGL(k_red_lookup, dim3(ngrid(R)), dim3(BLK), 0, ctx->stream,
-                     sk, kw, starts, 0, gid, R, op->st, found, miss);
-  exclusive_scan_u32_ns(ctx, miss, misspos, R);
-  hipLaunchKernelGGL(k_red_insert, dim3(ngrid(R)), dim3(BLK), 0, ctx->stream,
-                     sk, kw, starts, 0, gid, R, miss, misspos, 0,
-                     op->d_nrows, op->d_err, op->st);
-  u64 cap_out = 2 * R + 16;  // at most two rows per changed key
-  u64 *pk = dnew<u64>(ctx, cap_out * kw);
-  u8 *pvv = (u8 *)dmalloc(ctx, cap_out * ovb);
-  u64 *pt = dnew<u64>(ctx, cap_out);
-  i64 *pd = dnew<i64>(ctx, cap_out);
-  unsigned long long *ocount = (unsigned long long *)S.get(8);
-  fill_u64(ctx, (u64 *)ocount, 1, 0);
+  Groups g = group_sorted(ctx, sk, kw, tt, R);
+  Upsert up = kt_upsert(ctx, op->tbl, sk, g, R);
+  CorrBuf cb = corr_alloc(ctx, 2 * R + 16, kw, ovb);  // ≤2 rows per key
   hipLaunchKernelGGL(k_collate_apply, dim3(ngrid(R)), dim3(BLK), 0,
-                     ctx->stream, sk, kw, perm, tp, td, tv, starts, gid, R, t,
-                     op->st, found, miss, misspos, op->d_nrows, L,
-                     op->d_err + 1, pk, (u64 *)pvv, pt, pd, ocount);
-  hipLaunchKernelGGL(k_bump_ctr, dim3(1), dim3(1), 0, ctx->stream,
-                     op->d_nrows, misspos, gid, R);
-  // the stitch's one readback: count, both error words, table rows
-  u64 *stage = (u64 *)ctx->pin;
-  HIP_CHECK(hipMemcpyAsync(stage, ocount, 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(stage + 1, op->d_err, 16, hipMemcpyDeviceToHost,
-                           ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(stage + 3, op->d_nrows, 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  u64 emitted = stage[0], cap_err = stage[1], part_err = stage[2];
-  op->n_rows = stage[3];
+                     ctx->stream, sk, kw, perm, tp, td, tv, g.starts, g.gid, R,
+                     t, op->tbl.st, up.found, up.miss, up.misspos,
+                     op->tbl.d_nrows, L, op->tbl.d_err + 1, cb.pk,
+                     (u64 *)cb.pv, cb.pt, cb.pd, cb.ocount);
+  kt_commit(ctx, op->tbl, up, g, R);
+  // the stitch's one readback: count, table rows, both error words
+  const u64 *h = corr_read(ctx, cb, op->tbl.d_nrows, 3);
+  u64 emitted = h[0], cap_err = h[2], part_err = h[3];
+  op->tbl.n_rows = h[1];
   release_parts();
   if (cap_err || part_err) {
-    for (void *p : {(void *)pk, (void *)pvv, (void *)pt, (void *)pd})
-      dfree(ctx, p);
-    fill_u64(ctx, op->d_err, 2, 0);
+    corr_free(ctx, cb);
+    fill_u64(ctx, op->tbl.d_err, 2, 0);
     ctx->err = cap_err ? "collation state capacity exceeded"
                        : "collation: key missing a reduction type";
     return -1;
   }
-  DevUpdates pin{pk, pvv, pt, pd, emitted};
-  u64 *ok;
-  u8 *ov;
-  u64 *ot;
-  i64 *od;
-  u64 Mc;
-  consolidate_dev(ctx, kw, ovb, pin, &ok, &ov, &ot, &od, &Mc);
-  for (void *p : {(void *)pk, (void *)pvv, (void *)pt, (void *)pd})
-    dfree(ctx, p);
-  *out = make_out(ok, ov, ot, od, Mc, kw, ovb);
+  *out = corr_finish(ctx, cb, emitted, false);
   return 0;
 }
 

@@ -152,3 +152,100 @@ def test_drop_entry_points_tear_down():
     nb, nu, by = g.arr_stats(a4)
     assert nu > 0
     g.close()
+
+
+def _mku2(keys, vals, t, diffs, rng):
+    """One push spanning the two timestamps 2t and 2t + 1, rows split
+    across both in arrival order (the operator sorts by time itself)."""
+    n = len(keys)
+    times = (2 * t + (rng.permutation(n) % 2)).astype(np.uint64)
+    return abi.make_updates(np.asarray(keys, np.int64), vals, times,
+                            np.asarray(diffs, np.int64), 2 * t, 2 * t + 2)
+
+
+def _assert_same(a, b, msg):
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x.view(np.uint8), y.view(np.uint8),
+                                      err_msg=msg)
+
+
+def test_tables_grow_mid_multi_timestamp_stream():
+    """Growth decided from the host mirror while every push is cut into
+    two time slices: six pushes of 100 rows over moving keys, so the
+    reduce table (32 rows) and the threshold table (64 rows) each grow
+    at least twice between multi-slice pushes."""
+    os.environ["MZ_GPU_RED_CAP"] = "32"
+    os.environ["MZ_GPU_THR_CAP"] = "64"
+    try:
+        from materialize_amd._ffi import GpuCtx
+        from pyoracle import OracleCtx
+        g, o = GpuCtx(), OracleCtx()
+        aggs = [abi.Aggregate(func=abi.MZ_AGG_SUM_I64, off=0, width=8,
+                              is_float=0, nullable=0)]
+        spec = abi.reduce_spec(aggs, abi.schema(1, 8))
+        gred, ored = g.reduce_create(spec), o.reduce_create(spec)
+        sch = abi.schema(1, 8)
+        gthr, othr = g.threshold_create(sch), o.threshold_create(sch)
+        rng = np.random.default_rng(17)
+        n = 100
+        live = []  # threshold records currently present, oldest first
+        for t in range(6):
+            # reduce: keys move by 60 per push, as in the growth test above
+            keys = (rng.integers(0, 60, n) + 60 * t).astype(np.int64)
+            vals = rng.integers(0, 50, n).astype(np.int64) \
+                .reshape(-1, 1).view(np.uint8).reshape(n, 8)
+            diffs = rng.choice([-1, 1, 1], n).astype(np.int64)
+            trng = np.random.default_rng(100 + t)
+            a = g.reduce_push(gred, _mku2(keys, vals, t, diffs, trng))
+            trng = np.random.default_rng(100 + t)
+            b = o.reduce_push(ored, _mku2(keys, vals, t, diffs, trng))
+            _assert_same(a, b, f"reduce t={t}")
+            # threshold: fresh records in, the 40 oldest retracted to zero
+            old = live[:40]
+            live = live[len(old):]
+            fresh = list(range(t * 100, t * 100 + n - len(old)))
+            live += fresh
+            tk = np.asarray(fresh + old, np.int64)
+            tv = (tk % 7).reshape(-1, 1).view(np.uint8).reshape(n, 8)
+            td = np.asarray([1] * len(fresh) + [-1] * len(old), np.int64)
+            trng = np.random.default_rng(200 + t)
+            a = g.threshold_push(gthr, _mku2(tk, tv, t, td, trng))
+            trng = np.random.default_rng(200 + t)
+            b = o.threshold_push(othr, _mku2(tk, tv, t, td, trng))
+            _assert_same(a, b, f"threshold t={t}")
+        g.close()
+        o.close()
+    finally:
+        del os.environ["MZ_GPU_RED_CAP"]
+        del os.environ["MZ_GPU_THR_CAP"]
+
+
+def test_reduce_push2_matches_oracle():
+    """reduce_push2 at operator level: two streams of 50 rows enter one
+    push; one push has an empty first stream, one has both empty."""
+    from materialize_amd._ffi import GpuCtx
+    from pyoracle import OracleCtx
+    g, o = GpuCtx(), OracleCtx()
+    aggs = [abi.Aggregate(func=abi.MZ_AGG_COUNT, off=0, width=8,
+                          is_float=0, nullable=0),
+            abi.Aggregate(func=abi.MZ_AGG_SUM_I64, off=0, width=8,
+                          is_float=0, nullable=0)]
+    spec = abi.reduce_spec(aggs, abi.schema(1, 8))
+    gop, oop = g.reduce_create(spec), o.reduce_create(spec)
+    rng = np.random.default_rng(19)
+
+    def stream(n, t):
+        keys = rng.integers(0, 20, n).astype(np.int64)
+        vals = rng.integers(-50, 50, n).astype(np.int64) \
+            .reshape(-1, 1).view(np.uint8).reshape(n, 8)
+        return _mku(keys, vals, t, rng.choice([-1, 1, 1], n))
+
+    for t, (n1, n2) in enumerate([(50, 50), (0, 50), (0, 0), (50, 50)]):
+        u1, u2 = stream(n1, t), stream(n2, t)
+        a = g.reduce_push2_dev(gop, u1, u2)
+        b = o.reduce_push2_dev(oop, u1, u2)
+        _assert_same(a.to_host(), b.to_host(), f"t={t}")
+        a.release()
+        b.release()
+    g.close()
+    o.close()
