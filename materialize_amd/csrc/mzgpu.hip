@@ -525,87 +525,56 @@ struct BatchList {
 
 enum ProbeMode { PM_JOIN = 0, PM_HALF_LE = 1, PM_HALF_LT = 2 };
 
-// Count the output rows of one (delta row, batch) pair: walk the key's
-// val range applying the closure filter and the time mode. Returns
-// ok_count | err_count << 32 (err = closure evaluation errors, the
-// could_error split of linear_join.rs:495-541).
-__device__ __forceinline__ u64 d_count_pair(const DevBatch &b, int allpass,
-                                            const u64 *key, const u8 *dv,
-                                            u64 t, u64 kvr, int mode,
-                                            int swap,
-                                            const mz_gpu_closure &cl,
-                                            u32 lvb) {
-  u32 c = 0, e = 0;
-  for (u32 j = (u32)kvr; j < (u32)(kvr >> 32); j++) {
-    const u8 *lv = b.vals ? b.vals + (u64)j * lvb : nullptr;
-    const u8 *v1 = swap ? lv : dv;
-    const u8 *v2 = swap ? dv : lv;
-    int cls = d_closure_apply(&cl, key, v1, v2, nullptr, nullptr);
-    if (cls == 0) continue;
-    u32 lo = b.vu_off[j], hi = b.vu_off[j + 1];
-    u32 m;
-    if (mode == PM_JOIN || allpass) {
-      m = hi - lo;
-    } else {
-      m = 0;
-      for (u32 u = lo; u < hi; u++) {
-        u64 t2 = b.times[u];
-        m += (mode == PM_HALF_LE) ? (t2 <= t) : (t2 < t);
-      }
-    }
-    if (cls == 1)
-      c += m;
-    else
-      e += m;
+// The delta stream as every probe kernel takes it (by value). A Row is
+// also what the fused path's second stage probes with: its intermediate
+// row, held in registers.
+struct DeltaView {
+  const u64 *keys;
+  const u8 *vals;  // null when the stream carries no val
+  u32 vb;
+  const u64 *times;
+  const i64 *diffs;
+  u64 n;
+  u32 kw;
+  struct Row {
+    const u64 *key;
+    const u8 *val;
+    u64 t;
+    i64 d;
+  };
+  __device__ __forceinline__ Row row(u64 i) const {
+    return {keys + i * kw, vals ? vals + i * vb : nullptr, times[i],
+            diffs[i]};
   }
-  return (u64)c | ((u64)e << 32);
+};
+
+// Time mode. A PM_JOIN probe and an allpass batch keep every update; the
+// half-join modes keep those with t2 <= t (le) or t2 < t (lt).
+// Number of kept updates in [lo, hi):
+__device__ __forceinline__ u32 d_time_count(const DevBatch &b, int allpass,
+                                            int mode, u32 lo, u32 hi,
+                                            u64 t) {
+  if (mode == PM_JOIN || allpass) return hi - lo;
+  u32 m = 0;
+  for (u32 u = lo; u < hi; u++) {
+    u64 t2 = b.times[u];
+    m += (mode == PM_HALF_LE) ? (t2 <= t) : (t2 < t);
+  }
+  return m;
 }
 
-// Emit the counted rows at queue offsets *o (ok) / *eo (err) — ok fields
-// written straight to global (closure filters run before any field
-// write); error rows carry (code, time, d1*d2).
-__device__ __forceinline__ void d_emit_pair(const DevBatch &b, int allpass,
-                                            const u64 *key, const u8 *dv,
-                                            u64 t, i64 d1, u64 kvr,
-                                            int mode, int swap,
-                                            const mz_gpu_closure &cl,
-                                            u32 lvb, u32 okw, u32 ovb,
-                                            u64 *o, u64 *okeys, u8 *ovals,
-                                            u64 *otimes, i64 *odiffs,
-                                            u64 *eo, u64 *ecodes,
-                                            u64 *etimes, i64 *ediffs) {
-  for (u32 j = (u32)kvr; j < (u32)(kvr >> 32); j++) {
-    const u8 *lv = b.vals ? b.vals + (u64)j * lvb : nullptr;
-    const u8 *v1 = swap ? lv : dv;
-    const u8 *v2 = swap ? dv : lv;
-    int cls = d_closure_apply(&cl, key, v1, v2, nullptr, nullptr);
-    if (cls == 0) continue;
-    for (u32 u = b.vu_off[j]; u < b.vu_off[j + 1]; u++) {
-      u64 tout;
-      if (allpass) {
-        tout = t;
-      } else if (mode == PM_JOIN) {
-        u64 t2 = b.times[u];
-        tout = t2 > t ? t2 : t;
-      } else {
-        u64 t2 = b.times[u];
-        if (!((mode == PM_HALF_LE) ? (t2 <= t) : (t2 < t))) continue;
-        tout = t;
-      }
-      if (cls == 2) {
-        ecodes[*eo] = MZ_ERR_DIVISION_BY_ZERO;
-        etimes[*eo] = tout;
-        ediffs[*eo] = wmul(d1, b.diffs[u]);
-        (*eo)++;
-        continue;
-      }
-      (void)d_closure_apply(&cl, key, v1, v2, okeys + *o * okw,
-                            ovals + *o * ovb);
-      otimes[*o] = tout;
-      odiffs[*o] = wmul(d1, b.diffs[u]);
-      (*o)++;
-    }
+// Output time of update u in *tout, or false when the mode filters it.
+__device__ __forceinline__ bool d_time_out(const DevBatch &b, int allpass,
+                                           int mode, u32 u, u64 t,
+                                           u64 *tout) {
+  *tout = t;
+  if (allpass) return true;
+  u64 t2 = b.times[u];
+  if (mode == PM_JOIN) {
+    if (t2 > t) *tout = t2;
+    return true;
   }
+  return (mode == PM_HALF_LE) ? (t2 <= t) : (t2 < t);
 }
 
 // Wave-aggregated output-queue reservation: exclusive prefix of c across
@@ -624,6 +593,98 @@ __device__ __forceinline__ u64 wave_reserve(unsigned long long *ctr, u32 c,
   if (lane == 63 && wtotal)
     basell = (long long)atomicAdd(ctr, wtotal);
   return (u64)__shfl((int64_t)basell, 63, 64) + excl;
+}
+
+// Device half of the probe protocol: reserve c entries
+// of the first queue and e of the second (ALL 64 lanes must call), and
+// tell whether this lane has anything to write and both slices fit.
+// ctr[0]/ctr[1] accumulate the EXACT totals whether or not a slice fits;
+// a lane whose slice would cross a capacity skips its writes, and the
+// host relaunches once at the exact counts.
+__device__ __forceinline__ bool queue_reserve(unsigned long long *ctr,
+                                              u64 cap, u64 cap2, u32 c,
+                                              u32 e, u32 lane, u64 *o,
+                                              u64 *eo) {
+  *o = wave_reserve(ctr, c, lane);
+  *eo = wave_reserve(ctr + 1, e, lane);
+  return (c | e) && *o + c <= cap && *eo + e <= cap2;
+}
+
+// The fixed-width probes' output, passed to the kernels by value: an
+// ok-row queue of cap rows and an error-row queue of ecap rows.
+struct EmitQueue {
+  u64 cap, ecap;
+  unsigned long long *ctr;  // [0] ok rows, [1] error rows
+  u64 *okeys;
+  u8 *ovals;
+  u64 *otimes;
+  i64 *odiffs;
+  u64 *ecodes, *etimes;
+  i64 *ediffs;
+  __device__ __forceinline__ bool reserve(u32 c, u32 e, u32 lane, u64 *o,
+                                          u64 *eo) const {
+    return queue_reserve(ctr, cap, ecap, c, e, lane, o, eo);
+  }
+};
+
+// Count the output rows of one (delta row, batch) pair: walk the key's
+// val range applying the closure filter and the time mode. Returns
+// ok_count | err_count << 32 (err = closure evaluation errors, the
+// could_error split of linear_join.rs:495-541).
+__device__ __forceinline__ u64 d_count_pair(const DevBatch &b, int allpass,
+                                            const DeltaView::Row &r,
+                                            u64 kvr, int mode, int swap,
+                                            const mz_gpu_closure &cl,
+                                            u32 lvb) {
+  u32 c = 0, e = 0;
+  for (u32 j = (u32)kvr; j < (u32)(kvr >> 32); j++) {
+    const u8 *lv = b.vals ? b.vals + (u64)j * lvb : nullptr;
+    const u8 *v1 = swap ? lv : r.val;
+    const u8 *v2 = swap ? r.val : lv;
+    int cls = d_closure_apply(&cl, r.key, v1, v2, nullptr, nullptr);
+    if (cls == 0) continue;
+    u32 m = d_time_count(b, allpass, mode, b.vu_off[j], b.vu_off[j + 1], r.t);
+    if (cls == 1)
+      c += m;
+    else
+      e += m;
+  }
+  return (u64)c | ((u64)e << 32);
+}
+
+// Emit the counted rows at queue offsets *o (ok) / *eo (err) — ok fields
+// written straight to global (closure filters run before any field
+// write); error rows carry (code, time, d1*d2).
+__device__ __forceinline__ void d_emit_pair(const DevBatch &b, int allpass,
+                                            const DeltaView::Row &r,
+                                            u64 kvr, int mode, int swap,
+                                            const mz_gpu_closure &cl,
+                                            u32 lvb, u32 okw, u32 ovb,
+                                            const EmitQueue &q, u64 *o,
+                                            u64 *eo) {
+  for (u32 j = (u32)kvr; j < (u32)(kvr >> 32); j++) {
+    const u8 *lv = b.vals ? b.vals + (u64)j * lvb : nullptr;
+    const u8 *v1 = swap ? lv : r.val;
+    const u8 *v2 = swap ? r.val : lv;
+    int cls = d_closure_apply(&cl, r.key, v1, v2, nullptr, nullptr);
+    if (cls == 0) continue;
+    for (u32 u = b.vu_off[j]; u < b.vu_off[j + 1]; u++) {
+      u64 tout;
+      if (!d_time_out(b, allpass, mode, u, r.t, &tout)) continue;
+      if (cls == 2) {
+        q.ecodes[*eo] = MZ_ERR_DIVISION_BY_ZERO;
+        q.etimes[*eo] = tout;
+        q.ediffs[*eo] = wmul(r.d, b.diffs[u]);
+        (*eo)++;
+        continue;
+      }
+      (void)d_closure_apply(&cl, r.key, v1, v2, q.okeys + *o * okw,
+                            q.ovals + *o * ovb);
+      q.otimes[*o] = tout;
+      q.odiffs[*o] = wmul(r.d, b.diffs[u]);
+      (*o)++;
+    }
+  }
 }
 
 // canonical key order: i64-tuple ascending
@@ -650,15 +711,11 @@ __device__ __forceinline__ int d_key_cmp(const u64 *a, const u64 *b,
 // cap = exact count on overflow (rare; capacity hint kept per
 // arrangement).
 #define PROBE_TILE 4
-__global__ void k_probe_walk(const u64 *dkeys, const u8 *dvals, u32 dvb,
-                             const u64 *dtimes, const i64 *ddiffs, u64 n,
-                             u32 kw, u32 lvb, BatchList bl, int mode,
-                             int swap, const mz_gpu_closure cl, u64 cap,
-                             u64 ecap, unsigned long long *ctr,
-                             u64 *okeys, u8 *ovals, u64 *otimes,
-                             i64 *odiffs, u64 *ecodes, u64 *etimes,
-                             i64 *ediffs) {
+__global__ void k_probe_walk(DeltaView d, u32 lvb, BatchList bl, int mode,
+                             int swap, const mz_gpu_closure cl,
+                             EmitQueue q) {
   u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  u64 n = d.n;
   u64 total = n * (u64)bl.n;
   u64 stride = (u64)gridDim.x * blockDim.x;
   u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
@@ -681,7 +738,7 @@ __global__ void k_probe_walk(const u64 *dkeys, const u8 *dvals, u32 dvb,
         int bi = (int)(idx / n);
         const DevBatch &b = bl.b[bi];
         kvr[tt] = hash_lookup_range(b.hash, b.hash_slots,
-                                    dkeys + (idx % n) * kw, kw);
+                                    d.keys + (idx % n) * d.kw, d.kw);
       }
     }
     // Phase B: count matches per slot (filters applied); low 32 bits ok
@@ -693,30 +750,23 @@ __global__ void k_probe_walk(const u64 *dkeys, const u8 *dvals, u32 dvb,
       u64 idx = start + (it0 + tt) * stride;
       u64 i = idx % n;
       int bi = (int)(idx / n);
-      cc[tt] = d_count_pair(bl.b[bi], bl.allpass[bi], dkeys + i * kw,
-                            dvals ? dvals + i * dvb : nullptr, dtimes[i],
-                            kvr[tt], mode, swap, cl, lvb);
+      cc[tt] = d_count_pair(bl.b[bi], bl.allpass[bi], d.row(i), kvr[tt],
+                            mode, swap, cl, lvb);
       csum += (u32)cc[tt];
       esum += (u32)(cc[tt] >> 32);
     }
-    u64 base = wave_reserve(ctr, csum, lane);
-    u64 ebase = wave_reserve(ctr + 1, esum, lane);
-    if ((csum == 0 && esum == 0) || base + csum > cap ||
-        ebase + esum > ecap)
-      continue;
+    u64 o, eo;
+    if (!q.reserve(csum, esum, lane, &o, &eo)) continue;
     // Phase C: emit from L2-hot lines, fields written straight to the
     // reserved global slots (closure filters run before any field write)
-    u64 o = base, eo = ebase;
 #pragma unroll
     for (int tt = 0; tt < PROBE_TILE; tt++) {
       if (cc[tt] == 0) continue;
       u64 idx = start + (it0 + tt) * stride;
       u64 i = idx % n;
       int bi = (int)(idx / n);
-      d_emit_pair(bl.b[bi], bl.allpass[bi], dkeys + i * kw,
-                  dvals ? dvals + i * dvb : nullptr, dtimes[i], ddiffs[i],
-                  kvr[tt], mode, swap, cl, lvb, okw, ovb, &o, okeys, ovals,
-                  otimes, odiffs, &eo, ecodes, etimes, ediffs);
+      d_emit_pair(bl.b[bi], bl.allpass[bi], d.row(i), kvr[tt], mode, swap,
+                  cl, lvb, okw, ovb, q, &o, &eo);
     }
   }
 }
@@ -735,30 +785,22 @@ __global__ void k_probe_walk(const u64 *dkeys, const u8 *dvals, u32 dvb,
 // ctr[2] counts intermediate rows (stats/roofline only).
 #define P2_MAX_KW 2
 #define P2_MAX_VB 48
-#define P2_TILE 4
 
 // Count one (delta row, stage-1 batch) pair's final emissions through
 // both stages; returns ok | err<<32 and adds this pair's intermediate
 // row count to *inter (stats).
 __device__ __forceinline__ u64 d_path2_count(
-    const u64 *key, const u8 *dv, u64 t, const DevBatch &b1, int allpass1,
-    u64 kvr1, int mode1, const mz_gpu_closure &cl1, u32 lvb1, u32 k2w,
+    const DeltaView::Row &r, const DevBatch &b1, int allpass1, u64 kvr1,
+    int mode1, const mz_gpu_closure &cl1, u32 lvb1, u32 k2w,
     const BatchList &bl2, int mode2, const mz_gpu_closure &cl2, u32 lvb2,
     u64 *inter) {
   u32 c = 0, e = 0;
   for (u32 j = (u32)kvr1; j < (u32)(kvr1 >> 32); j++) {
     const u8 *lv = b1.vals ? b1.vals + (u64)j * lvb1 : nullptr;
-    int cls = d_closure_apply(&cl1, key, dv, lv, nullptr, nullptr);
+    int cls = d_closure_apply(&cl1, r.key, r.val, lv, nullptr, nullptr);
     if (cls == 0) continue;
-    u32 lo = b1.vu_off[j], hi = b1.vu_off[j + 1];
-    u32 m1 = 0;
-    if (allpass1) {
-      m1 = hi - lo;
-    } else {
-      for (u32 u = lo; u < hi; u++)
-        m1 += (mode1 == PM_HALF_LE) ? (b1.times[u] <= t)
-                                    : (b1.times[u] < t);
-    }
+    u32 m1 = d_time_count(b1, allpass1, mode1, b1.vu_off[j],
+                          b1.vu_off[j + 1], r.t);
     if (m1 == 0) continue;
     if (cls == 2) {
       e += m1;
@@ -767,12 +809,12 @@ __device__ __forceinline__ u64 d_path2_count(
     *inter += m1;
     u64 k2[P2_MAX_KW];
     u8 v2buf[P2_MAX_VB];
-    (void)d_closure_apply(&cl1, key, dv, lv, k2, v2buf);
+    (void)d_closure_apply(&cl1, r.key, r.val, lv, k2, v2buf);
     for (int b2i = 0; b2i < bl2.n; b2i++) {
       const DevBatch &b2 = bl2.b[b2i];
       u64 kvr2 = hash_lookup_range(b2.hash, b2.hash_slots, k2, k2w);
       if (kvr2 == ~0ull) continue;
-      u64 ce2 = d_count_pair(b2, bl2.allpass[b2i], k2, v2buf, t, kvr2,
+      u64 ce2 = d_count_pair(b2, bl2.allpass[b2i], {k2, v2buf, r.t, 0}, kvr2,
                              mode2, 0, cl2, lvb2);
       c += m1 * (u32)ce2;
       e += m1 * (u32)(ce2 >> 32);
@@ -784,28 +826,28 @@ __device__ __forceinline__ u64 d_path2_count(
 // Emit one pair's rows at queue offsets *o / *eo (same nested walk as
 // the count — ranges are L2-hot on this second pass).
 __device__ __forceinline__ void d_path2_emit(
-    const u64 *key, const u8 *dv, u64 t, i64 d0, const DevBatch &b1,
-    int allpass1, u64 kvr1, int mode1, const mz_gpu_closure &cl1, u32 lvb1,
-    u32 k2w, const BatchList &bl2, int mode2, const mz_gpu_closure &cl2,
-    u32 lvb2, u32 okw, u32 ovb, u64 *o, u64 *okeys, u8 *ovals, u64 *otimes,
-    i64 *odiffs, u64 *eo, u64 *ecodes, u64 *etimes, i64 *ediffs) {
+    const DeltaView::Row &r, const DevBatch &b1, int allpass1, u64 kvr1,
+    int mode1, const mz_gpu_closure &cl1, u32 lvb1, u32 k2w,
+    const BatchList &bl2, int mode2, const mz_gpu_closure &cl2, u32 lvb2,
+    u32 okw, u32 ovb, const EmitQueue &q, u64 *o, u64 *eo) {
   for (u32 j = (u32)kvr1; j < (u32)(kvr1 >> 32); j++) {
     const u8 *lv = b1.vals ? b1.vals + (u64)j * lvb1 : nullptr;
-    int cls = d_closure_apply(&cl1, key, dv, lv, nullptr, nullptr);
+    int cls = d_closure_apply(&cl1, r.key, r.val, lv, nullptr, nullptr);
     if (cls == 0) continue;
     u64 k2[P2_MAX_KW];
     u8 v2buf[P2_MAX_VB];
-    if (cls == 1) (void)d_closure_apply(&cl1, key, dv, lv, k2, v2buf);
+    if (cls == 1) (void)d_closure_apply(&cl1, r.key, r.val, lv, k2, v2buf);
     u32 lo = b1.vu_off[j], hi = b1.vu_off[j + 1];
     for (u32 u = lo; u < hi; u++) {
-      if (!allpass1 && !((mode1 == PM_HALF_LE) ? (b1.times[u] <= t)
-                                               : (b1.times[u] < t)))
-        continue;
-      i64 d1 = wmul(d0, b1.diffs[u]);
+      // half-join modes never promote the time: a kept update's output
+      // time is r.t itself
+      u64 tout;
+      if (!d_time_out(b1, allpass1, mode1, u, r.t, &tout)) continue;
+      i64 d1 = wmul(r.d, b1.diffs[u]);
       if (cls == 2) {
-        ecodes[*eo] = MZ_ERR_DIVISION_BY_ZERO;
-        etimes[*eo] = t;
-        ediffs[*eo] = d1;
+        q.ecodes[*eo] = MZ_ERR_DIVISION_BY_ZERO;
+        q.etimes[*eo] = r.t;
+        q.ediffs[*eo] = d1;
         (*eo)++;
         continue;
       }
@@ -813,39 +855,36 @@ __device__ __forceinline__ void d_path2_emit(
         const DevBatch &b2 = bl2.b[b2i];
         u64 kvr2 = hash_lookup_range(b2.hash, b2.hash_slots, k2, k2w);
         if (kvr2 == ~0ull) continue;
-        d_emit_pair(b2, bl2.allpass[b2i], k2, v2buf, t, d1, kvr2, mode2,
-                    0, cl2, lvb2, okw, ovb, o, okeys, ovals, otimes,
-                    odiffs, eo, ecodes, etimes, ediffs);
+        d_emit_pair(b2, bl2.allpass[b2i], {k2, v2buf, r.t, d1}, kvr2, mode2,
+                    0, cl2, lvb2, okw, ovb, q, o, eo);
       }
     }
   }
 }
 
-__global__ void k_probe_path2(const u64 *dkeys, const u8 *dvals, u32 dvb,
-                              const u64 *dtimes, const i64 *ddiffs, u64 n,
-                              u32 kw, u32 lvb1, BatchList bl1, int mode1,
-                              const mz_gpu_closure cl1, u32 lvb2,
+__global__ void k_probe_path2(DeltaView d, u32 lvb1, BatchList bl1,
+                              int mode1, const mz_gpu_closure cl1, u32 lvb2,
                               BatchList bl2, int mode2,
-                              const mz_gpu_closure cl2, u64 cap, u64 ecap,
-                              unsigned long long *ctr, u64 *okeys,
-                              u8 *ovals, u64 *otimes, i64 *odiffs,
-                              u64 *ecodes, u64 *etimes, i64 *ediffs) {
+                              const mz_gpu_closure cl2, EmitQueue q) {
   u32 okw = cl2.out.key_words, ovb = cl2.out.val_bytes;
   u32 k2w = cl1.out.key_words;
+  u64 n = d.n;
   u64 total = n * (u64)bl1.n;
   u64 stride = (u64)gridDim.x * blockDim.x;
   u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
   u64 iters = (total + stride - 1) / stride;  // uniform across the wave
   u32 lane = threadIdx.x & 63;
-  // P2_TILE pairs per macro-iteration (same shape as k_probe_walk):
+  // PROBE_TILE pairs per macro-iteration — the loop of k_probe_walk,
+  // repeated here because sharing it through an inlined function cost
+  // both kernels registers ("Probe-protocol refactor"):
   // phase A issues the independent stage-1 hash lines, phase B walks the
   // nested counts, ONE wave-aggregated reservation per tile, phase C
   // emits from L2-hot ranges.
-  for (u64 it0 = 0; it0 < iters; it0 += P2_TILE) {
-    u64 kvr1[P2_TILE];
-    u64 cc[P2_TILE];
+  for (u64 it0 = 0; it0 < iters; it0 += PROBE_TILE) {
+    u64 kvr1[PROBE_TILE];
+    u64 cc[PROBE_TILE];
 #pragma unroll
-    for (int tt = 0; tt < P2_TILE; tt++) {
+    for (int tt = 0; tt < PROBE_TILE; tt++) {
       u64 idx = start + (it0 + tt) * stride;
       kvr1[tt] = ~0ull;
       cc[tt] = 0;
@@ -853,43 +892,36 @@ __global__ void k_probe_path2(const u64 *dkeys, const u8 *dvals, u32 dvb,
         int bi = (int)(idx / n);
         const DevBatch &b = bl1.b[bi];
         kvr1[tt] = hash_lookup_range(b.hash, b.hash_slots,
-                                     dkeys + (idx % n) * kw, kw);
+                                     d.keys + (idx % n) * d.kw, d.kw);
       }
     }
     u32 csum = 0, esum = 0;
     u64 inter = 0;
 #pragma unroll
-    for (int tt = 0; tt < P2_TILE; tt++) {
+    for (int tt = 0; tt < PROBE_TILE; tt++) {
       if (kvr1[tt] == ~0ull) continue;
       u64 idx = start + (it0 + tt) * stride;
       u64 i = idx % n;
       int bi = (int)(idx / n);
-      cc[tt] = d_path2_count(dkeys + i * kw,
-                             dvals ? dvals + i * dvb : nullptr, dtimes[i],
-                             bl1.b[bi], bl1.allpass[bi], kvr1[tt], mode1,
-                             cl1, lvb1, k2w, bl2, mode2, cl2, lvb2,
+      cc[tt] = d_path2_count(d.row(i), bl1.b[bi], bl1.allpass[bi], kvr1[tt],
+                             mode1, cl1, lvb1, k2w, bl2, mode2, cl2, lvb2,
                              &inter);
       csum += (u32)cc[tt];
       esum += (u32)(cc[tt] >> 32);
     }
-    u64 base = wave_reserve(ctr, csum, lane);
-    u64 ebase = wave_reserve(ctr + 1, esum, lane);
-    if (inter) atomicAdd(ctr + 2, (unsigned long long)inter);
-    if ((csum == 0 && esum == 0) || base + csum > cap ||
-        ebase + esum > ecap)
-      continue;
-    u64 o = base, eo = ebase;
+    u64 o, eo;
+    bool fits = q.reserve(csum, esum, lane, &o, &eo);
+    if (inter) atomicAdd(q.ctr + 2, (unsigned long long)inter);
+    if (!fits) continue;
 #pragma unroll
-    for (int tt = 0; tt < P2_TILE; tt++) {
+    for (int tt = 0; tt < PROBE_TILE; tt++) {
       if (cc[tt] == 0) continue;
       u64 idx = start + (it0 + tt) * stride;
       u64 i = idx % n;
       int bi = (int)(idx / n);
-      d_path2_emit(dkeys + i * kw, dvals ? dvals + i * dvb : nullptr,
-                   dtimes[i], ddiffs[i], bl1.b[bi], bl1.allpass[bi],
-                   kvr1[tt], mode1, cl1, lvb1, k2w, bl2, mode2, cl2, lvb2,
-                   okw, ovb, &o, okeys, ovals, otimes, odiffs, &eo,
-                   ecodes, etimes, ediffs);
+      d_path2_emit(d.row(i), bl1.b[bi], bl1.allpass[bi], kvr1[tt], mode1,
+                   cl1, lvb1, k2w, bl2, mode2, cl2, lvb2, okw, ovb, q, &o,
+                   &eo);
     }
   }
 }
@@ -941,15 +973,12 @@ __global__ void k_merge_bounds(const u64 *dkeys, u64 n, u32 kw,
   }
 }
 
-__global__ void k_probe_merge(const u64 *dkeys, const u8 *dvals, u32 dvb,
-                              const u64 *dtimes, const i64 *ddiffs, u64 n,
-                              u32 kw, u32 lvb, DevBatch b, int allpass,
+__global__ void k_probe_merge(DeltaView d, u32 lvb, DevBatch b, int allpass,
                               int mode, int swap, const mz_gpu_closure cl,
-                              const u64 *bounds, u64 cap, u64 ecap,
-                              unsigned long long *ctr, u64 *okeys,
-                              u8 *ovals, u64 *otimes, i64 *odiffs,
-                              u64 *ecodes, u64 *etimes, i64 *ediffs) {
+                              const u64 *bounds, EmitQueue q) {
   __shared__ u64 lk[MERGE_LDSW];
+  u64 n = d.n;
+  u32 kw = d.kw;
   u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
   u64 r0 = (u64)blockIdx.x * MERGE_DROWS;
   if (r0 >= n) return;
@@ -967,12 +996,12 @@ __global__ void k_probe_merge(const u64 *dkeys, const u8 *dvals, u32 dvb,
   u64 kvr[RPT];
   u64 cc[RPT];
   u32 csum = 0, esum = 0;
-  for (int q = 0; q < RPT; q++) {
-    u64 i = r0 + threadIdx.x + (u64)q * blockDim.x;  // coalesced
-    kvr[q] = ~0ull;
-    cc[q] = 0;
+  for (int s = 0; s < RPT; s++) {
+    u64 i = r0 + threadIdx.x + (u64)s * blockDim.x;  // coalesced
+    kvr[s] = ~0ull;
+    cc[s] = 0;
     if (i < r1) {
-      const u64 *key = dkeys + i * kw;
+      const u64 *key = d.keys + i * kw;
       const u64 *base = use_lds ? lk : b.keys + klo * kw;
       u64 lo = 0, hi = nk;
       while (lo < hi) {
@@ -984,28 +1013,21 @@ __global__ void k_probe_merge(const u64 *dkeys, const u8 *dvals, u32 dvb,
       }
       if (lo < nk && d_key_cmp(base + lo * kw, key, kw) == 0) {
         u64 kidx = klo + lo;
-        kvr[q] = (u64)b.kv_off[kidx] | ((u64)b.kv_off[kidx + 1] << 32);
-        cc[q] = d_count_pair(b, allpass, key,
-                             dvals ? dvals + i * dvb : nullptr, dtimes[i],
-                             kvr[q], mode, swap, cl, lvb);
-        csum += (u32)cc[q];
-        esum += (u32)(cc[q] >> 32);
+        kvr[s] = (u64)b.kv_off[kidx] | ((u64)b.kv_off[kidx + 1] << 32);
+        cc[s] = d_count_pair(b, allpass, d.row(i), kvr[s], mode, swap, cl,
+                             lvb);
+        csum += (u32)cc[s];
+        esum += (u32)(cc[s] >> 32);
       }
     }
   }
-  u64 base_o = wave_reserve(ctr, csum, lane);
-  u64 base_e = wave_reserve(ctr + 1, esum, lane);
-  if ((csum == 0 && esum == 0) || base_o + csum > cap ||
-      base_e + esum > ecap)
-    return;
-  u64 o = base_o, eo = base_e;
-  for (int q = 0; q < RPT; q++) {
-    if (!cc[q]) continue;
-    u64 i = r0 + threadIdx.x + (u64)q * blockDim.x;
-    d_emit_pair(b, allpass, dkeys + i * kw,
-                dvals ? dvals + i * dvb : nullptr, dtimes[i], ddiffs[i],
-                kvr[q], mode, swap, cl, lvb, okw, ovb, &o, okeys, ovals,
-                otimes, odiffs, &eo, ecodes, etimes, ediffs);
+  u64 o, eo;
+  if (!q.reserve(csum, esum, lane, &o, &eo)) return;
+  for (int s = 0; s < RPT; s++) {
+    if (!cc[s]) continue;
+    u64 i = r0 + threadIdx.x + (u64)s * blockDim.x;
+    d_emit_pair(b, allpass, d.row(i), kvr[s], mode, swap, cl, lvb, okw, ovb,
+                q, &o, &eo);
   }
 }
 
@@ -2893,6 +2915,14 @@ mz_gpu_out *make_out(u64 *k, u8 *v, u64 *t, i64 *d, u64 n, u32 kw, u32 vb) {
   return &o->pub_;
 }
 
+mz_gpu_out *make_out_vl(u64 *k, u8 *arena, u32 *voffs, u64 *t, i64 *d,
+                        u64 n, u64 bytes, u32 kw) {
+  mz_gpu_out *o = make_out(k, arena, t, d, n, kw, 0xFFFFFFFFu);
+  o->val_offs = voffs;
+  o->val_arena_bytes = bytes;
+  return o;
+}
+
 // Attach a consolidated error stream to an out-batch (ownership moves).
 void out_attach_errs(mz_gpu_out *out, u64 *codes, u64 *times, i64 *diffs,
                      u64 n) {
@@ -2992,6 +3022,15 @@ void consolidate_dev(Ctx *c, u32 kw, u32 vb, DevUpdates in, u64 **okeys,
 mz_gpu_out *empty_out(Ctx *c, u32 kw, u32 vb) {
   return make_out(dnew<u64>(c, 1), (u8 *)dmalloc(c, 1), dnew<u64>(c, 1),
                   dnew<i64>(c, 1), 0, kw, vb);
+}
+
+// the varlen empty result: zero rows, val_offs = [0]
+mz_gpu_out *empty_out_vl(Ctx *c, u32 kw) {
+  mz_gpu_out *o = make_out_vl(dnew<u64>(c, 1), (u8 *)dmalloc(c, 1),
+                              dnew<u32>(c, 1), dnew<u64>(c, 1),
+                              dnew<i64>(c, 1), 0, 0, kw);
+  fill_u32(c, o->val_offs, 1, 0);
+  return o;
 }
 
 // Key groups of a slice of m rows sorted by (time, key): gid is the
@@ -3839,14 +3878,27 @@ static const bool _mrvl_registered = [] {
 // bytes, reserves both queues per wave, emits key fields + passthrough
 // varlen val bytes. The closure must not reference the varlen (lookup)
 // side except as the single whole-val passthrough (validated host-side).
-__global__ void k_probe_vl(const u64 *dkeys, const u8 *dvals, u32 dvb,
-                           const u64 *dtimes, const i64 *ddiffs, u64 n,
-                           u32 kw, BatchList bl, int mode, int swap,
-                           const mz_gpu_closure cl, u64 cap, u64 bcap,
-                           unsigned long long *ctr, u64 *okeys,
-                           u32 *ovstarts, u32 *ovends, u8 *oarena,
-                           u64 *otimes, i64 *odiffs) {
+// Its second queue is the val arena (bytes), not errors: the same
+// reservation (queue_reserve) over ctr[0] rows / ctr[1] bytes.
+struct VlQueue {
+  u64 cap, bcap;
+  unsigned long long *ctr;  // [0] rows, [1] arena bytes
+  u64 *okeys;
+  u32 *ovstarts, *ovends;
+  u8 *oarena;
+  u64 *otimes;
+  i64 *odiffs;
+  __device__ __forceinline__ bool reserve(u32 c, u32 bytes, u32 lane,
+                                          u64 *o, u64 *bo) const {
+    return queue_reserve(ctr, cap, bcap, c, bytes, lane, o, bo);
+  }
+};
+
+__global__ void k_probe_vl(DeltaView d, BatchList bl, int mode, int swap,
+                           const mz_gpu_closure cl, VlQueue q) {
   u32 okw = cl.out.key_words;
+  u64 n = d.n;
+  u32 kw = d.kw;
   u64 total = n * (u64)bl.n;
   u64 stride = (u64)gridDim.x * blockDim.x;
   u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
@@ -3864,45 +3916,37 @@ __global__ void k_probe_vl(const u64 *dkeys, const u8 *dvals, u32 dvb,
       i = idx % n;
       bi = (int)(idx / n);
       const DevBatch &b = bl.b[bi];
-      const u64 *key = dkeys + i * kw;
-      const u8 *dv = dvals ? dvals + i * dvb : nullptr;
+      const u64 *key = d.keys + i * kw;
+      const u8 *dv = d.vals ? d.vals + i * d.vb : nullptr;
       cls = d_closure_apply(&cl, key, swap ? nullptr : dv,
                             swap ? dv : nullptr, nullptr, nullptr);
       if (cls == 1) {
         kvr = hash_lookup_range(b.hash, b.hash_slots, key, kw);
         if (kvr != ~0ull) {
-          u64 t = dtimes[i];
+          u64 t = d.times[i];
           for (u32 j = (u32)kvr; j < (u32)(kvr >> 32); j++) {
             u32 len = b.v_offs[j + 1] - b.v_offs[j];
-            u32 lo = b.vu_off[j], hi = b.vu_off[j + 1];
-            u32 m;
-            if (mode == PM_JOIN || bl.allpass[bi]) {
-              m = hi - lo;
-            } else {
-              m = 0;
-              for (u32 u = lo; u < hi; u++) {
-                u64 t2 = b.times[u];
-                m += (mode == PM_HALF_LE) ? (t2 <= t) : (t2 < t);
-              }
-            }
+            u32 m = d_time_count(b, bl.allpass[bi], mode, b.vu_off[j],
+                                 b.vu_off[j + 1], t);
             c += m;
             bytes += m * len;
           }
         }
       }
     }
-    u64 base = wave_reserve(ctr, c, lane);
-    u64 bbase = wave_reserve(ctr + 1, bytes, lane);
-    if (c == 0 || base + c > cap || bbase + bytes > bcap) continue;
+    u64 o, bo;
+    if (!q.reserve(c, bytes, lane, &o, &bo)) continue;
     const DevBatch &b = bl.b[bi];
-    const u64 *key = dkeys + i * kw;
-    const u8 *dv = dvals ? dvals + i * dvb : nullptr;
-    u64 t = dtimes[i];
-    i64 d1 = ddiffs[i];
-    u64 o = base, bo = bbase;
+    DeltaView::Row r = d.row(i);
+    const u64 *key = r.key;
+    const u8 *dv = r.val;
+    u64 t = r.t;
+    i64 d1 = r.d;
     for (u32 j = (u32)kvr; j < (u32)(kvr >> 32); j++) {
       u32 vsrc = b.v_offs[j], len = b.v_offs[j + 1] - vsrc;
       for (u32 u = b.vu_off[j]; u < b.vu_off[j + 1]; u++) {
+        // d_time_out written out: calling it costs this kernel 2 VGPRs
+        // ("Probe-protocol refactor")
         u64 tout;
         if (bl.allpass[bi]) {
           tout = t;
@@ -3915,13 +3959,14 @@ __global__ void k_probe_vl(const u64 *dkeys, const u8 *dvals, u32 dvb,
           tout = t;
         }
         (void)d_closure_apply(&cl, key, swap ? nullptr : dv,
-                              swap ? dv : nullptr, okeys + o * okw,
-                              (u8 *)(okeys + o * okw));
-        otimes[o] = tout;
-        odiffs[o] = wmul(d1, b.diffs[u]);
-        ovstarts[o] = (u32)bo;
-        ovends[o] = (u32)(bo + len);
-        for (u32 cc = 0; cc < len; cc++) oarena[bo + cc] = b.vals[vsrc + cc];
+                              swap ? dv : nullptr, q.okeys + o * okw,
+                              (u8 *)(q.okeys + o * okw));
+        q.otimes[o] = tout;
+        q.odiffs[o] = wmul(d1, b.diffs[u]);
+        q.ovstarts[o] = (u32)bo;
+        q.ovends[o] = (u32)(bo + len);
+        for (u32 cc = 0; cc < len; cc++)
+          q.oarena[bo + cc] = b.vals[vsrc + cc];
         o++;
         bo += len;
       }
@@ -3929,16 +3974,177 @@ __global__ void k_probe_vl(const u64 *dkeys, const u8 *dvals, u32 dvb,
   }
 }
 
-mz_gpu_out *make_out_vl(u64 *k, u8 *arena, u32 *voffs, u64 *t, i64 *d,
-                        u64 n, u64 bytes, u32 kw) {
-  mz_gpu_out *o = make_out(k, arena, t, d, n, kw, 0xFFFFFFFFu);
-  o->val_offs = voffs;
-  o->val_arena_bytes = bytes;
-  return o;
-}
-
 static void arr_flush_impl(Ctx *ctx, mz_gpu_arr *a);
 static void arr_insert_vl(Ctx *ctx, mz_gpu_arr *a, const mz_gpu_updates *u);
+
+// ---- probe protocol, host half: the steps every probe
+// driver (probe_impl, probe_vl_impl, mz_gpu_halfjoin2) runs, each written
+// once.
+
+// Make a lookup arrangement ready to be probed on the ctx stream. A probe
+// after insert_async must see the batch (probes of the OLD state precede
+// the insert call entirely), and must run after the lookup lane's
+// enqueued maintenance. Exception (1-deep insert pipeline): a
+// time-filtered probe (le/lt half-join) whose delta times all precede a
+// pending batch's lower frontier cannot match any of its rows
+// (t2 >= lower >= delta.upper > t1), so the pending insert may keep
+// consolidating on its lane while this probe runs — skipping the flush
+// (and its lane sync) entirely. (Varlen arrangements never hold a pending
+// insert, so they always flush.)
+static void probe_prepare(Ctx *ctx, mz_gpu_arr *lk, int mode,
+                          u64 delta_upper) {
+  bool future_pending = (mode == PM_HALF_LE || mode == PM_HALF_LT) &&
+                        lk->pending.active && !lk->pending_merge.active &&
+                        lk->pending.lower >= delta_upper;
+  if (!future_pending) arr_flush_impl(ctx, lk);
+  if (lk->stream) (void)hipStreamWaitEvent(ctx->stream, lk->ev_ready, 0);
+}
+
+// Snapshot the probe-visible batches (see BatchList for allpass). A spine
+// deeper than the list catches up synchronously first — install any
+// deferred merge (its inputs are in the list being merged), then merge
+// everything into one batch. Defensive: every insert path already caps
+// the spine at 10 batches.
+static void build_probe_batchlist(Ctx *ctx, mz_gpu_arr *a, u64 delta_lower,
+                                  BatchList &bl) {
+  for (;;) {
+    bl.n = 0;
+    bool fits = true;
+    for (auto &b : a->batches) {
+      if (b.n_upds == 0) continue;
+      if (bl.n >= 12) {
+        fits = false;
+        break;
+      }
+      u64 tmax_excl = std::max(b.upper, a->logical_compaction + 1);
+      bl.allpass[bl.n] = tmax_excl <= delta_lower ? 1 : 0;
+      bl.b[bl.n++] = b;
+    }
+    if (fits) return;
+    if (a->pending_merge.active) {
+      if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
+      merge_install(ctx, a);
+    }
+    merge_range(ctx, a, 0, a->batches.size());
+  }
+}
+
+// Owning host side of the kernels' EmitQueue.
+struct ProbeQueue {
+  u32 okw, ovb;
+  EmitQueue q;
+  void alloc(Ctx *c, u64 cap, u64 ecap) {
+    q.cap = cap;
+    q.ecap = ecap;
+    q.okeys = dnew<u64>(c, cap * okw);
+    q.ovals = (u8 *)dmalloc(c, std::max<u64>(cap * ovb, 1));
+    q.otimes = dnew<u64>(c, cap);
+    q.odiffs = dnew<i64>(c, cap);
+    q.ecodes = dnew<u64>(c, ecap);
+    q.etimes = dnew<u64>(c, ecap);
+    q.ediffs = dnew<i64>(c, ecap);
+  }
+  void free_ok(Ctx *c) {
+    for (void *p : {(void *)q.okeys, (void *)q.ovals, (void *)q.otimes,
+                    (void *)q.odiffs})
+      dfree(c, p);
+  }
+  void free_errs(Ctx *c) {
+    for (void *p : {(void *)q.ecodes, (void *)q.etimes, (void *)q.ediffs})
+      dfree(c, p);
+  }
+  void free(Ctx *c) {
+    free_ok(c);
+    free_errs(c);
+  }
+};
+
+// ... and of the varlen probe's VlQueue (rows, arena bytes).
+struct VlProbeQueue {
+  u32 okw;
+  VlQueue q;
+  void alloc(Ctx *c, u64 cap, u64 bcap) {
+    q.cap = cap;
+    q.bcap = bcap;
+    q.okeys = dnew<u64>(c, cap * okw);
+    q.ovstarts = dnew<u32>(c, cap);
+    q.ovends = dnew<u32>(c, cap);
+    q.oarena = (u8 *)dmalloc(c, bcap);
+    q.otimes = dnew<u64>(c, cap);
+    q.odiffs = dnew<i64>(c, cap);
+  }
+  void free(Ctx *c) {
+    for (void *p : {(void *)q.okeys, (void *)q.ovstarts, (void *)q.ovends,
+                    (void *)q.oarena, (void *)q.otimes, (void *)q.odiffs})
+      dfree(c, p);
+  }
+};
+
+struct ProbeCounts {
+  u64 M, E;  // exact totals of the first / second queue
+  u64 I;     // third counter (the fused path's intermediates), else 0
+};
+
+// Run one probe: allocate pq at (cap, cap2), zero the nctr counters,
+// launch(pq.q), read the counters back. They are exact whether or not
+// the queues held them, so on overflow ONE relaunch at the exact counts
+// suffices and nothing is read again. With kernel timing on, the (last)
+// launch is bracketed by ev_a/ev_b and the call is entered in the probe
+// statistics as a probe of n delta rows.
+template <class Queue, class Launch>
+static ProbeCounts run_probe(Ctx *ctx, Queue &pq, u64 cap, u64 cap2,
+                             int nctr, u64 n, Launch launch) {
+  unsigned long long *ctr =
+      (unsigned long long *)(*ctx->scr).get(8 * nctr);
+  pq.q.ctr = ctr;
+  pq.alloc(ctx, cap, cap2);
+  auto shot = [&]() {
+    fill_u64(ctx, (u64 *)ctr, nctr, 0);
+    if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
+    launch(pq.q);
+    if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_b, ctx->stream));
+  };
+  shot();
+  unsigned long long *MB =
+      (unsigned long long *)d2h_pinned(ctx, ctr, 8 * nctr);
+  ProbeCounts r{MB[0], MB[1], nctr > 2 ? MB[2] : 0};
+  u64 launches = 1;
+  if (r.M > cap || r.E > cap2) {  // rare: queue overflow — exact relaunch
+    pq.free(ctx);
+    pq.alloc(ctx, std::max<u64>(r.M, 1), std::max<u64>(r.E, 1));
+    shot();
+    launches = 2;
+  }
+  if (ctx->time_kernels) {
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
+    ctx->probe_ms += ms;
+    ctx->probe_rows += n;
+    ctx->probe_launches += launches;
+    ctx->probe_pairs += r.M;
+  }
+  return r;
+}
+
+// Error stream of a finished probe: consolidate the E raw rows by
+// (code, time) — the err collection is a first-class update stream in
+// the reference (linear_join.rs:516-541) — free the raw columns, attach.
+static void attach_err_stream(Ctx *ctx, mz_gpu_out *out, ProbeQueue &pq,
+                              u64 E) {
+  u64 *cek = nullptr, *cet = nullptr;
+  i64 *ced = nullptr;
+  u64 Ec = 0;
+  if (E) {
+    DevUpdates epin{pq.q.ecodes, nullptr, pq.q.etimes, pq.q.ediffs, E};
+    u8 *unused_v;
+    consolidate_dev(ctx, 1, 0, epin, &cek, &unused_v, &cet, &ced, &Ec);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    dfree(ctx, unused_v);
+  }
+  pq.free_errs(ctx);
+  out_attach_errs(out, cek, cet, ced, Ec);
+}
 
 // varlen probe host path (halfjoin / linear join over a varlen lookup):
 // validates the closure shape, runs k_probe_vl with row+byte queues,
@@ -3947,11 +4153,7 @@ static int probe_vl_impl(Ctx *ctx, mz_gpu_arr *lookup,
                          const mz_gpu_updates *u, u32 stream_vb, int mode,
                          int swap, const mz_gpu_closure *cl,
                          mz_gpu_out **out) {
-  arr_flush_impl(ctx, lookup);
-  if (lookup->stream)
-    (void)hipStreamWaitEvent(ctx->stream, lookup->ev_ready, 0);
-  (*ctx->scr).reset();
-  auto &S = (*ctx->scr);
+  probe_prepare(ctx, lookup, mode, u->upper);
   u32 kw = lookup->schema.kw;
   u32 okw = cl->out.key_words;
   // closure validation: no reference to the varlen side except the
@@ -3977,71 +4179,29 @@ static int probe_vl_impl(Ctx *ctx, mz_gpu_arr *lookup,
   }
   mz_gpu_closure cl2 = *cl;
   cl2.n_val_fields = 0;  // key fields evaluated in-kernel; val is copied
-  DevUpdates d = stage_updates(ctx, u, kw, stream_vb);
   BatchList bl;
-  bl.n = 0;
-  for (auto &b : lookup->batches) {
-    if (b.n_upds == 0) continue;
-    if (bl.n >= 12) {
-      merge_range(ctx, lookup, 0, lookup->batches.size());
-      return probe_vl_impl(ctx, lookup, u, stream_vb, mode, swap, cl, out);
-    }
-    u64 tmax_excl = std::max(b.upper, lookup->logical_compaction + 1);
-    bl.allpass[bl.n] = tmax_excl <= u->lower ? 1 : 0;
-    bl.b[bl.n++] = b;
-  }
+  build_probe_batchlist(ctx, lookup, u->lower, bl);
+  (*ctx->scr).reset();
+  DevUpdates d = stage_updates(ctx, u, kw, stream_vb);
   u64 n = d.n;
   if (n == 0 || bl.n == 0) {
-    *out = make_out_vl(dnew<u64>(ctx, 1), (u8 *)dmalloc(ctx, 1),
-                       dnew<u32>(ctx, 1), dnew<u64>(ctx, 1),
-                       dnew<i64>(ctx, 1), 0, 0, okw);
-    fill_u32(ctx, (*out)->val_offs, 1, 0);
+    *out = empty_out_vl(ctx, okw);
     return 0;
   }
-  u64 nb2 = n * (u64)bl.n;
   u64 cap = 2 * n + 1024;
-  u64 bcap = 64 * cap;
-  unsigned long long *ctr = (unsigned long long *)S.get(16);
-  u64 *pk = dnew<u64>(ctx, cap * okw);
-  u32 *pvs = dnew<u32>(ctx, cap);
-  u32 *pve = dnew<u32>(ctx, cap);
-  u8 *pa = (u8 *)dmalloc(ctx, bcap);
-  u64 *pt = dnew<u64>(ctx, cap);
-  i64 *pd = dnew<i64>(ctx, cap);
-  for (int attempt = 0; attempt < 2; attempt++) {
-    fill_u64(ctx, (u64 *)ctr, 2, 0);
-    hipLaunchKernelGGL(k_probe_vl, dim3(ngrid(nb2)), dim3(BLK), 0,
-                       ctx->stream, d.keys, d.vals, stream_vb, d.times,
-                       d.diffs, n, kw, bl, mode, swap, cl2, cap, bcap, ctr,
-                       pk, pvs, pve, pa, pt, pd);
-    unsigned long long MB[2];
-    HIP_CHECK(hipMemcpyAsync(MB, ctr, 16, hipMemcpyDeviceToHost,
-                             ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (MB[0] <= cap && MB[1] <= bcap) {
-      VlCols cc = consolidate_vl(ctx, okw, pk, pvs, pve, pa, pt, pd,
-                                 MB[0]);
-      for (void *p : {(void *)pk, (void *)pvs, (void *)pve, (void *)pa,
-                      (void *)pt, (void *)pd})
-        dfree(ctx, p);
-      *out = make_out_vl(cc.keys, cc.arena, cc.voffs, cc.times, cc.diffs,
-                         cc.n, cc.bytes, okw);
-      return 0;
-    }
-    for (void *p : {(void *)pk, (void *)pvs, (void *)pve, (void *)pa,
-                    (void *)pt, (void *)pd})
-      dfree(ctx, p);
-    cap = std::max<u64>(MB[0], 1);
-    bcap = std::max<u64>(MB[1], 1);
-    pk = dnew<u64>(ctx, cap * okw);
-    pvs = dnew<u32>(ctx, cap);
-    pve = dnew<u32>(ctx, cap);
-    pa = (u8 *)dmalloc(ctx, bcap);
-    pt = dnew<u64>(ctx, cap);
-    pd = dnew<i64>(ctx, cap);
-  }
-  ctx->err = "varlen probe: queue overflow after exact relaunch";
-  return -1;
+  DeltaView dv{d.keys, d.vals, stream_vb, d.times, d.diffs, n, kw};
+  VlProbeQueue pq{okw};
+  ProbeCounts r = run_probe(ctx, pq, cap, 64 * cap, 2, n, [&](VlQueue q) {
+    hipLaunchKernelGGL(k_probe_vl, dim3(ngrid(n * (u64)bl.n)), dim3(BLK), 0,
+                       ctx->stream, dv, bl, mode, swap, cl2, q);
+  });
+  VlCols cc = consolidate_vl(ctx, okw, pq.q.okeys, pq.q.ovstarts,
+                             pq.q.ovends, pq.q.oarena, pq.q.otimes,
+                             pq.q.odiffs, r.M);
+  pq.free(ctx);
+  *out = make_out_vl(cc.keys, cc.arena, cc.voffs, cc.times, cc.diffs, cc.n,
+                     cc.bytes, okw);
+  return 0;
 }
 
 struct mz_gpu_ctx {
@@ -4811,46 +4971,14 @@ static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
                       mz_gpu_out **out) {
   if (is_varlen(lookup->schema.vb))
     return probe_vl_impl(ctx, lookup, u, stream_vb, mode, swap, cl, out);
-  // a probe after insert_async must see the batch (probes of the OLD
-  // state precede the insert call entirely), and must run after the
-  // lookup lane's enqueued maintenance. Exception (1-deep insert
-  // pipeline): a time-filtered probe (le/lt half-join) whose delta times
-  // all precede a pending batch's lower frontier cannot match any of its
-  // rows (t2 >= lower >= delta.upper > t1), so the pending insert may
-  // keep consolidating on its lane while this probe runs — skipping the
-  // flush (and its lane sync) entirely.
-  bool future_pending =
-      (mode == PM_HALF_LE || mode == PM_HALF_LT) &&
-      lookup->pending.active && !lookup->pending_merge.active &&
-      lookup->pending.lower >= u->upper;
-  if (!future_pending) arr_flush_impl(ctx, lookup);
-  if (lookup->stream)
-    (void)hipStreamWaitEvent(ctx->stream, lookup->ev_ready, 0);
+  probe_prepare(ctx, lookup, mode, u->upper);
+  BatchList bl;
+  build_probe_batchlist(ctx, lookup, u->lower, bl);
   (*ctx->scr).reset();
   auto &S = (*ctx->scr);
   u32 kw = lookup->schema.kw, lvb = lookup->schema.vb;
   u32 okw = cl->out.key_words, ovb = cl->out.val_bytes;
   DevUpdates d = stage_updates(ctx, u, kw, stream_vb);
-  BatchList bl;
-  bl.n = 0;
-  for (auto &b : lookup->batches) {
-    if (b.n_upds == 0) continue;
-    if (bl.n >= 12) {
-      // too many batches: catch up synchronously (install any deferred
-      // merge first — its inputs are in the list being merged)
-      if (lookup->pending_merge.active) {
-        if (lookup->mstream)
-          HIP_CHECK(hipStreamSynchronize(lookup->mstream));
-        merge_install(ctx, lookup);
-      }
-      merge_range(ctx, lookup, 0, lookup->batches.size());
-      return probe_impl(ctx, lookup, u, stream_vb, mode, swap, cl,
-                        consolidate_out, out);
-    }
-    u64 tmax_excl = std::max(b.upper, lookup->logical_compaction + 1);
-    bl.allpass[bl.n] = tmax_excl <= u->lower ? 1 : 0;
-    bl.b[bl.n++] = b;
-  }
   u64 n = d.n;
   if (n == 0 || bl.n == 0) {
     *out = empty_out(ctx, okw, ovb);
@@ -4886,20 +5014,6 @@ static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
   }
   u64 nb2 = n * (u64)blw.n;
   u64 mgrid = (n + MERGE_DROWS - 1) / MERGE_DROWS;
-  // Single-walk probe: allocate the output queue from the arrangement's
-  // emit-ratio hint, relaunch once with the exact count on overflow.
-  u64 cap = (lookup->probe_cap_hint ? lookup->probe_cap_hint + 1 : 2) * n +
-            1024;
-  u64 ecap = n / 4 + 1024;  // error rows are exceptional; exact relaunch
-  unsigned long long *ctr = (unsigned long long *)S.get(16);
-  fill_u64(ctx, (u64 *)ctr, 2, 0);  // [0] ok rows, [1] err rows
-  u64 *pk = dnew<u64>(ctx, cap * okw);
-  u8 *pv = (u8 *)dmalloc(ctx, std::max<u64>(cap * ovb, 1));
-  u64 *pt = dnew<u64>(ctx, cap);
-  i64 *pd = dnew<i64>(ctx, cap);
-  u64 *ek = dnew<u64>(ctx, ecap);
-  u64 *et = dnew<u64>(ctx, ecap);
-  i64 *ed = dnew<i64>(ctx, ecap);
   u64 *mbounds = nullptr;
   if (!mts.empty()) {
     mbounds = (u64 *)S.get(mts.size() * mgrid * 2 * 8);
@@ -4909,55 +5023,26 @@ static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
                          mts[mi].b.n_keys, mgrid,
                          mbounds + mi * mgrid * 2);
   }
-  auto launch_probes = [&]() {
-    for (size_t mi = 0; mi < mts.size(); mi++)
-      hipLaunchKernelGGL(k_probe_merge, dim3((u32)mgrid), dim3(BLK), 0,
-                         ctx->stream, d.keys, d.vals, stream_vb, d.times,
-                         d.diffs, n, kw, lvb, mts[mi].b,
-                         (int)mts[mi].allpass, mode, swap, *cl,
-                         mbounds + mi * mgrid * 2, cap, ecap, ctr, pk, pv,
-                         pt, pd, ek, et, ed);
-    if (blw.n)
-      hipLaunchKernelGGL(k_probe_walk, dim3(ngrid(nb2)), dim3(BLK), 0,
-                         ctx->stream, d.keys, d.vals, stream_vb, d.times,
-                         d.diffs, n, kw, lvb, blw, mode, swap, *cl, cap,
-                         ecap, ctr, pk, pv, pt, pd, ek, et, ed);
-  };
-  if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
-  launch_probes();
-  if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_b, ctx->stream));
-  unsigned long long *MB =
-      (unsigned long long *)d2h_pinned(ctx, ctr, 16);
-  u64 M = MB[0], E = MB[1];
-  u64 launches = 1;
-  if (M > cap || E > ecap) {  // rare: queue overflow — exact relaunch
-    for (void *p : {(void *)pk, (void *)pv, (void *)pt, (void *)pd,
-                    (void *)ek, (void *)et, (void *)ed})
-      dfree(ctx, p);
-    cap = std::max<u64>(M, 1);
-    ecap = std::max<u64>(E, 1);
-    pk = dnew<u64>(ctx, cap * okw);
-    pv = (u8 *)dmalloc(ctx, std::max<u64>(cap * ovb, 1));
-    pt = dnew<u64>(ctx, cap);
-    pd = dnew<i64>(ctx, cap);
-    ek = dnew<u64>(ctx, ecap);
-    et = dnew<u64>(ctx, ecap);
-    ed = dnew<i64>(ctx, ecap);
-    fill_u64(ctx, (u64 *)ctr, 2, 0);
-    if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
-    launch_probes();
-    if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_b, ctx->stream));
-    launches = 2;
-  }
+  // Queue sized from the arrangement's emit-ratio hint; error rows are
+  // exceptional (exact relaunch).
+  u64 cap = (lookup->probe_cap_hint ? lookup->probe_cap_hint + 1 : 2) * n +
+            1024;
+  DeltaView dv{d.keys, d.vals, stream_vb, d.times, d.diffs, n, kw};
+  ProbeQueue pq{okw, ovb};
+  ProbeCounts r =
+      run_probe(ctx, pq, cap, n / 4 + 1024, 2, n, [&](EmitQueue q) {
+        for (size_t mi = 0; mi < mts.size(); mi++)
+          hipLaunchKernelGGL(k_probe_merge, dim3((u32)mgrid), dim3(BLK), 0,
+                             ctx->stream, dv, lvb, mts[mi].b,
+                             (int)mts[mi].allpass, mode, swap, *cl,
+                             mbounds + mi * mgrid * 2, q);
+        if (blw.n)
+          hipLaunchKernelGGL(k_probe_walk, dim3(ngrid(nb2)), dim3(BLK), 0,
+                             ctx->stream, dv, lvb, blw, mode, swap, *cl, q);
+      });
+  u64 M = r.M;
   lookup->probe_cap_hint = (M + n - 1) / n;
-  if (ctx->time_kernels) {
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
-    ctx->probe_ms += ms;
-    ctx->probe_rows += n;
-    ctx->probe_launches += launches;
-    ctx->probe_pairs += M;
+  if (ctx->time_kernels) {  // run_probe has synced and entered the call
     ctx->probe_batches += (u64)bl.n;
     // Algorithmic bytes of the probe (SURVEY §8d model, updated for the
     // compressed 16 B hash slots: one 64 B line per probed batch instead
@@ -4968,38 +5053,23 @@ static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
         n * (8ull * kw + stream_vb + 16) + n * 64ull * (u64)bl.n +
         M * (lvb + 16ull) + M * (8ull * okw + ovb + 16);
   }
-  // error stream: consolidate by (code, time) — the err collection is a
-  // first-class update stream in the reference (linear_join.rs:516-541)
-  u64 *cek = nullptr, *cet = nullptr;
-  i64 *ced = nullptr;
-  u64 Ec = 0;
-  if (E) {
-    DevUpdates epin{ek, nullptr, et, ed, E};
-    u8 *unused_v;
-    consolidate_dev(ctx, 1, 0, epin, &cek, &unused_v, &cet, &ced, &Ec);
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    dfree(ctx, unused_v);
-  }
-  for (void *p : {(void *)ek, (void *)et, (void *)ed}) dfree(ctx, p);
   if (!consolidate_out) {
     // raw emitted pairs (deterministic content; consumer consolidates)
-    *out = make_out(pk, pv, pt, pd, M, okw, ovb);
-    out_attach_errs(*out, cek, cet, ced, Ec);
-    return 0;
+    *out = make_out(pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M,
+                    okw, ovb);
+  } else {
+    DevUpdates pin{pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M};
+    u64 *ok;
+    u8 *ov;
+    u64 *ot;
+    i64 *od;
+    u64 Mc;
+    consolidate_dev(ctx, okw, ovb, pin, &ok, &ov, &ot, &od, &Mc);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    pq.free_ok(ctx);
+    *out = make_out(ok, ov, ot, od, Mc, okw, ovb);
   }
-  // consolidate the emitted pairs
-  DevUpdates pin{pk, pv, pt, pd, M};
-  u64 *ok;
-  u8 *ov;
-  u64 *ot;
-  i64 *od;
-  u64 Mc;
-  consolidate_dev(ctx, okw, ovb, pin, &ok, &ov, &ot, &od, &Mc);
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  for (void *p : {(void *)pk, (void *)pv, (void *)pt, (void *)pd})
-    dfree(ctx, (p));
-  *out = make_out(ok, ov, ot, od, Mc, okw, ovb);
-  out_attach_errs(*out, cek, cet, ced, Ec);
+  attach_err_stream(ctx, *out, pq, r.E);
   return 0;
 }
 
@@ -5059,28 +5129,6 @@ int mz_gpu_halfjoin_raw(mz_gpu_ctx *c, mz_gpu_arr *lookup,
                     le ? PM_HALF_LE : PM_HALF_LT, 0, cl, 0, out);
 }
 
-// Probe-visible BatchList (with the >12-batch synchronous catch-up of
-// probe_impl); returns false after a catch-up merge — retry.
-static bool build_probe_batchlist(Ctx *ctx, mz_gpu_arr *a, u64 delta_lower,
-                                  BatchList &bl) {
-  bl.n = 0;
-  for (auto &b : a->batches) {
-    if (b.n_upds == 0) continue;
-    if (bl.n >= 12) {
-      if (a->pending_merge.active) {
-        if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
-        merge_install(ctx, a);
-      }
-      merge_range(ctx, a, 0, a->batches.size());
-      return false;
-    }
-    u64 tmax_excl = std::max(b.upper, a->logical_compaction + 1);
-    bl.allpass[bl.n] = tmax_excl <= delta_lower ? 1 : 0;
-    bl.b[bl.n++] = b;
-  }
-  return true;
-}
-
 // Fused two-stage delta path (k_probe_path2): delta -> lookup1 (le1) ->
 // lookup2 (le2), raw (unconsolidated) output with the err stream
 // attached. The render layer uses this when a DeltaPathPlan has exactly
@@ -5102,19 +5150,14 @@ int mz_gpu_halfjoin2(mz_gpu_ctx *c, mz_gpu_arr *lk1, int le1,
     ctx->err = "halfjoin2: stage-1 closure output shape unsupported";
     return 1;
   }
-  for (mz_gpu_arr *lk : {lk1, lk2}) {
-    bool future_pending = lk->pending.active &&
-                          !lk->pending_merge.active &&
-                          lk->pending.lower >= u->upper;
-    if (!future_pending) arr_flush_impl(ctx, lk);
-    if (lk->stream)
-      (void)hipStreamWaitEvent(ctx->stream, lk->ev_ready, 0);
-  }
+  int mode1 = le1 ? PM_HALF_LE : PM_HALF_LT;
+  int mode2 = le2 ? PM_HALF_LE : PM_HALF_LT;
+  probe_prepare(ctx, lk1, mode1, u->upper);
+  probe_prepare(ctx, lk2, mode2, u->upper);
   BatchList bl1, bl2;
-  while (!build_probe_batchlist(ctx, lk1, u->lower, bl1)) {}
-  while (!build_probe_batchlist(ctx, lk2, u->lower, bl2)) {}
+  build_probe_batchlist(ctx, lk1, u->lower, bl1);
+  build_probe_batchlist(ctx, lk2, u->lower, bl2);
   (*ctx->scr).reset();
-  auto &S = (*ctx->scr);
   u32 kw = lk1->schema.kw, lvb1 = lk1->schema.vb, lvb2 = lk2->schema.vb;
   u32 okw = cl2->out.key_words, ovb = cl2->out.val_bytes;
   DevUpdates d = stage_updates(ctx, u, kw, stream_vb);
@@ -5123,63 +5166,19 @@ int mz_gpu_halfjoin2(mz_gpu_ctx *c, mz_gpu_arr *lk1, int le1,
     *out = empty_out(ctx, okw, ovb);
     return 0;
   }
-  int mode1 = le1 ? PM_HALF_LE : PM_HALF_LT;
-  int mode2 = le2 ? PM_HALF_LE : PM_HALF_LT;
   u64 cap = (lk1->path_cap_hint ? lk1->path_cap_hint + 1 : 2) * n + 1024;
-  u64 ecap = n / 4 + 1024;
-  unsigned long long *ctr = (unsigned long long *)S.get(24);
-  fill_u64(ctx, (u64 *)ctr, 3, 0);  // [0] ok, [1] err, [2] intermediates
-  u64 *pk = dnew<u64>(ctx, cap * okw);
-  u8 *pv = (u8 *)dmalloc(ctx, std::max<u64>(cap * ovb, 1));
-  u64 *pt = dnew<u64>(ctx, cap);
-  i64 *pd = dnew<i64>(ctx, cap);
-  u64 *ek = dnew<u64>(ctx, ecap);
-  u64 *et = dnew<u64>(ctx, ecap);
-  i64 *ed = dnew<i64>(ctx, ecap);
-  u64 total = n * (u64)bl1.n;
-  auto launch = [&]() {
-    hipLaunchKernelGGL(k_probe_path2, dim3(ngrid(total)), dim3(BLK), 0,
-                       ctx->stream, d.keys, d.vals, stream_vb, d.times,
-                       d.diffs, n, kw, lvb1, bl1, mode1, *cl1, lvb2, bl2,
-                       mode2, *cl2, cap, ecap, ctr, pk, pv, pt, pd, ek,
-                       et, ed);
-  };
-  if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
-  launch();
-  if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_b, ctx->stream));
-  unsigned long long *MB = (unsigned long long *)d2h_pinned(ctx, ctr, 24);
-  u64 M = MB[0], E = MB[1], I = MB[2];
-  u64 launches = 1;
-  if (M > cap || E > ecap) {  // rare: queue overflow — exact relaunch
-    for (void *p : {(void *)pk, (void *)pv, (void *)pt, (void *)pd,
-                    (void *)ek, (void *)et, (void *)ed})
-      dfree(ctx, p);
-    cap = std::max<u64>(M, 1);
-    ecap = std::max<u64>(E, 1);
-    pk = dnew<u64>(ctx, cap * okw);
-    pv = (u8 *)dmalloc(ctx, std::max<u64>(cap * ovb, 1));
-    pt = dnew<u64>(ctx, cap);
-    pd = dnew<i64>(ctx, cap);
-    ek = dnew<u64>(ctx, ecap);
-    et = dnew<u64>(ctx, ecap);
-    ed = dnew<i64>(ctx, ecap);
-    fill_u64(ctx, (u64 *)ctr, 3, 0);
-    if (ctx->time_kernels)
-      HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
-    launch();
-    if (ctx->time_kernels)
-      HIP_CHECK(hipEventRecord(ctx->ev_b, ctx->stream));
-    launches = 2;
-  }
+  DeltaView dv{d.keys, d.vals, stream_vb, d.times, d.diffs, n, kw};
+  ProbeQueue pq{okw, ovb};
+  // counters: [0] ok, [1] err, [2] intermediates
+  ProbeCounts r =
+      run_probe(ctx, pq, cap, n / 4 + 1024, 3, n, [&](EmitQueue q) {
+        hipLaunchKernelGGL(k_probe_path2, dim3(ngrid(n * (u64)bl1.n)),
+                           dim3(BLK), 0, ctx->stream, dv, lvb1, bl1, mode1,
+                           *cl1, lvb2, bl2, mode2, *cl2, q);
+      });
+  u64 M = r.M, I = r.I;
   lk1->path_cap_hint = (M + n - 1) / n;
-  if (ctx->time_kernels) {
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
-    ctx->probe_ms += ms;
-    ctx->probe_rows += n;
-    ctx->probe_launches += launches;
-    ctx->probe_pairs += M;
+  if (ctx->time_kernels) {  // run_probe has synced and entered the call
     ctx->probe_batches += (u64)bl1.n + (u64)bl2.n;
     // algorithmic bytes: delta tuple + one hash line per stage-1 batch
     // + matched stage-1 val/upds + one hash line per stage-2 batch per
@@ -5190,19 +5189,9 @@ int mz_gpu_halfjoin2(mz_gpu_ctx *c, mz_gpu_arr *lk1, int le1,
         I * (lvb1 + 16ull) + I * 64ull * (u64)bl2.n +
         M * (lvb2 + 16ull) + M * (8ull * okw + ovb + 16);
   }
-  u64 *cek = nullptr, *cet = nullptr;
-  i64 *ced = nullptr;
-  u64 Ec = 0;
-  if (E) {
-    DevUpdates epin{ek, nullptr, et, ed, E};
-    u8 *unused_v;
-    consolidate_dev(ctx, 1, 0, epin, &cek, &unused_v, &cet, &ced, &Ec);
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    dfree(ctx, unused_v);
-  }
-  for (void *p : {(void *)ek, (void *)et, (void *)ed}) dfree(ctx, p);
-  *out = make_out(pk, pv, pt, pd, M, okw, ovb);
-  out_attach_errs(*out, cek, cet, ced, Ec);
+  *out = make_out(pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M, okw,
+                  ovb);
+  attach_err_stream(ctx, *out, pq, r.E);
   return 0;
 }
 
