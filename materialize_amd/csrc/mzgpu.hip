@@ -2706,67 +2706,6 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
                              c->stream));
     std::swap(perm, perm_out);
   }
-  if (getenv("MZ_DBG_SORT") && n) {
-    // diagnostic: host-side validation of the produced permutation
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    fprintf(stderr, "[dbg_sort] n=%llu kw=%u vb=%u tm=%d vwords=%u "
-            "passes=%zu chunks=%zu\n", (unsigned long long)n, kw, vb,
-            (int)time_major, vwords, passes.size(), chunks.size());
-    for (u32 s = 0; s < 1 + vwords + kw; s++)
-      fprintf(stderr, "[dbg_sort] slot %u min=%llx max=%llx\n", s,
-              (unsigned long long)hmin[s], (unsigned long long)hmax[s]);
-    std::vector<u32> hp(n);
-    std::vector<u64> hk(n * kw), ht(n);
-    std::vector<u8> hv(std::max<u64>(n * vb, 1));
-    HIP_CHECK(hipMemcpy(hp.data(), perm, n * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(hk.data(), keys, n * kw * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(ht.data(), times, n * 8, hipMemcpyDeviceToHost));
-    if (vb)
-      HIP_CHECK(hipMemcpy(hv.data(), vals, n * vb, hipMemcpyDeviceToHost));
-    std::vector<u8> seen(n, 0);
-    bool isperm = true;
-    for (u64 i = 0; i < n; i++) {
-      if (hp[i] >= n || seen[hp[i]]) { isperm = false; break; }
-      seen[hp[i]] = 1;
-    }
-    auto cmp_le = [&](u32 a, u32 b) {  // (time?,key,val) order per mode
-      auto keycmp = [&]() -> int {
-        for (u32 w = 0; w < kw; w++) {
-          i64 x = (i64)hk[(u64)a * kw + w], y = (i64)hk[(u64)b * kw + w];
-          if (x != y) return x < y ? -1 : 1;
-        }
-        return 0;
-      };
-      if (time_major) {
-        if (ht[a] != ht[b]) return ht[a] < ht[b];
-        int kc = keycmp();
-        return kc <= 0;
-      }
-      int kc = keycmp();
-      if (kc) return kc < 0;
-      for (u32 cbyte = 0; cbyte < vb; cbyte += 8) {
-        u64 x = 0, y = 0;
-        u32 rem = vb - cbyte < 8 ? vb - cbyte : 8;
-        memcpy(&x, hv.data() + (u64)a * vb + cbyte, rem);
-        memcpy(&y, hv.data() + (u64)b * vb + cbyte, rem);
-        if (x != y) return x < y;
-      }
-      if (ht[a] != ht[b]) return ht[a] < ht[b];
-      return true;
-    };
-    u64 bad = ~0ull;
-    for (u64 i = 0; i + 1 < n && bad == ~0ull; i++)
-      if (!cmp_le(hp[i], hp[i + 1])) bad = i;
-    fprintf(stderr, "[dbg_sort] perm_valid=%d sorted=%d bad_at=%lld\n",
-            (int)isperm, (int)(bad == ~0ull), (long long)bad);
-    if (bad != ~0ull) {
-      for (u64 i = (bad > 2 ? bad - 2 : 0); i < std::min(n, bad + 3); i++)
-        fprintf(stderr, "[dbg_sort]  i=%llu perm=%u key=%lld t=%llu\n",
-                (unsigned long long)i, hp[i],
-                (long long)hk[(u64)hp[i] * kw], (unsigned long long)ht[hp[i]]);
-    }
-    fflush(stderr);
-  }
 }
 
 // Bounds-checked scan input: in[i] for i < n, 0 for the padding slot —
@@ -2780,21 +2719,6 @@ struct ScanPadIn {
   }
 };
 
-u64 exclusive_scan_u32(Ctx *c, const u32 *in, u32 *out, u64 n) {
-  // returns total; out = exclusive prefix (out has n+1 slots).
-  auto &S = (*c->scr);
-  auto it = rocprim::make_transform_iterator(
-      rocprim::make_counting_iterator<u64>(0), ScanPadIn{in, n});
-  size_t need = 0;
-  (void)rocprim::exclusive_scan(nullptr, need, it, out, 0u, n + 1,
-                          rocprim::plus<u32>(), c->stream);
-  void *tmp = S.get(need);
-  (void)rocprim::exclusive_scan(tmp, need, it, out, 0u, n + 1,
-                          rocprim::plus<u32>(), c->stream);
-  u32 total = *(u32 *)d2h_pinned(c, out + n, 4);
-  return total;
-}
-
 // enqueue-only exclusive scan (out has n+1 slots; no readback)
 void exclusive_scan_u32_ns(Ctx *c, const u32 *in, u32 *out, u64 n) {
   auto &S = (*c->scr);
@@ -2806,6 +2730,12 @@ void exclusive_scan_u32_ns(Ctx *c, const u32 *in, u32 *out, u64 n) {
   void *tmp = S.get(need);
   (void)rocprim::exclusive_scan(tmp, need, it, out, 0u, n + 1,
                                 rocprim::plus<u32>(), c->stream);
+}
+
+// the same scan plus a synchronising read of the total
+u64 exclusive_scan_u32(Ctx *c, const u32 *in, u32 *out, u64 n) {
+  exclusive_scan_u32_ns(c, in, out, n);
+  return *(u32 *)d2h_pinned(c, out + n, 4);
 }
 
 __global__ void k_write_u64(u64 *p, u64 v) { *p = v; }
@@ -2932,18 +2862,95 @@ void out_attach_errs(mz_gpu_out *out, u64 *codes, u64 *times, i64 *diffs,
   out->err_diffs = diffs;
 }
 
-// Core consolidation: sort + group + sum + compact. Returns owned device
-// arrays (exact-size). Input must be device-resident.
-// Enqueue-only consolidation into CAPACITY-sized outputs (allocated by
-// the caller at n rows); dcounts[0] receives the consolidated row count
-// on device. The only host sync is the column-min/max read inside
-// sort_updates.
-void consolidate_with_perm(Ctx *c, u32 kw, u32 vb, DevUpdates in,
-                           const u32 *perm, u64 *okeys, u8 *ovals,
-                           u64 *otimes, i64 *odiffs, u64 *dcounts);
+// Flat columns: four owned device arrays with room for n rows (at least
+// one), the form consolidation writes and build_batch_core / make_out
+// take over.
+struct FlatCols {
+  u64 *keys = nullptr;
+  u8 *vals = nullptr;
+  u64 *times = nullptr;
+  i64 *diffs = nullptr;
+};
+FlatCols flat_alloc(Ctx *c, u64 n, u32 kw, u32 vb) {
+  u64 capn = std::max<u64>(n, 1);
+  FlatCols f;
+  f.keys = dnew<u64>(c, capn * kw);
+  f.vals = (u8 *)dmalloc(c, std::max<u64>(capn * vb, 1));
+  f.times = dnew<u64>(c, capn);
+  f.diffs = dnew<i64>(c, capn);
+  return f;
+}
+void flat_free(Ctx *c, FlatCols &f) {
+  for (void *p : {(void *)f.keys, (void *)f.vals, (void *)f.times,
+                  (void *)f.diffs})
+    dfree(c, p);
+  f = FlatCols();
+}
+// hand the columns over to an out-batch of n rows
+mz_gpu_out *make_out(const FlatCols &f, u64 n, u32 kw, u32 vb) {
+  return make_out(f.keys, f.vals, f.times, f.diffs, n, kw, vb);
+}
 
-void consolidate_core(Ctx *c, u32 kw, u32 vb, DevUpdates in, u64 *okeys,
-                      u8 *ovals, u64 *otimes, i64 *odiffs, u64 *dcounts,
+// Group n permuted rows by their head flags and sum each group's diffs
+// (wrapping), enqueue-only: starts[g] is the first row of group g, gid the
+// inclusive group-id scan, gsum[g] the group's sum, nz[g] whether it
+// survives and nzpos the exclusive scan of nz — nzpos[n] is the survivor
+// count, left on the device.
+struct GroupSums {
+  u32 *gid, *starts;
+  i64 *gsum;
+  u32 *nz, *nzpos;
+};
+GroupSums group_sum_by_perm(Ctx *c, const u32 *flags, const i64 *diffs,
+                            const u32 *perm, u64 n) {
+  auto &S = (*c->scr);
+  GroupSums g;
+  g.gid = (u32 *)S.get(n * 4);
+  inclusive_scan_u32(c, flags, g.gid, n);
+  g.starts = (u32 *)S.get(n * 4);
+  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     flags, g.gid, g.starts, n);
+  // wrapping inclusive prefix of permuted diffs
+  u64 *pdiff = (u64 *)S.get(n * 8);
+  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     (const u64 *)diffs, perm, pdiff, n);
+  u64 *pref = (u64 *)S.get(n * 8);
+  inclusive_scan_u64(c, pdiff, pref, n);
+  g.gsum = (i64 *)S.get(n * 8);
+  g.nz = (u32 *)S.get((n + 1) * 4);
+  hipLaunchKernelGGL(k_group_sums, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     g.starts, g.gid, n, pref, g.gsum, g.nz);
+  g.nzpos = (u32 *)S.get((n + 1) * 4);
+  exclusive_scan_u32_ns(c, g.nz, g.nzpos, n);
+  return g;
+}
+
+// Enqueue-only consolidation given a ready ordering permutation (group +
+// sum + compact) into CAPACITY-sized outputs (in.n rows); dcounts[0]
+// receives the consolidated row count on device.
+void consolidate_with_perm(Ctx *c, u32 kw, u32 vb, DevUpdates in,
+                           const u32 *perm, const FlatCols &o,
+                           u64 *dcounts) {
+  auto &S = (*c->scr);
+  u64 n = in.n;
+  if (n == 0) {
+    fill_u64(c, dcounts, 1, 0);
+    return;
+  }
+  u32 *flags = (u32 *)S.get(n * 4);
+  hipLaunchKernelGGL(k_head_flags, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     in.keys, kw, in.vals, vb, in.times, perm, flags, n, 1);
+  GroupSums g = group_sum_by_perm(c, flags, in.diffs, perm, n);
+  hipLaunchKernelGGL(k_emit_consolidated, dim3(ngrid(n)), dim3(BLK), 0,
+                     c->stream, in.keys, kw, in.vals, vb, in.times, perm,
+                     g.starts, g.gsum, g.nz, g.nzpos, g.gid, n, o.keys,
+                     o.vals, o.times, o.diffs, dcounts);
+}
+
+// Core consolidation: sort + group + sum + compact, enqueue-only but for
+// the column-min/max read inside sort_updates (none with a cached plan).
+void consolidate_core(Ctx *c, u32 kw, u32 vb, DevUpdates in,
+                      const FlatCols &o, u64 *dcounts,
                       mz_gpu_arr::SortPlan *plan = nullptr) {
   MZ_PROF(c, "consolidate_core");
   auto &S = (*c->scr);
@@ -2955,63 +2962,17 @@ void consolidate_core(Ctx *c, u32 kw, u32 vb, DevUpdates in, u64 *okeys,
   u32 *perm = (u32 *)S.get(n * 4);
   sort_updates(c, in.keys, kw, in.vals, vb, in.times, n, perm, false,
                plan);
-  consolidate_with_perm(c, kw, vb, in, perm, okeys, ovals, otimes, odiffs,
-                        dcounts);
-}
-
-// Consolidation given a ready ordering permutation (group + sum + compact).
-void consolidate_with_perm(Ctx *c, u32 kw, u32 vb, DevUpdates in,
-                           const u32 *perm, u64 *okeys, u8 *ovals,
-                           u64 *otimes, i64 *odiffs, u64 *dcounts) {
-  auto &S = (*c->scr);
-  u64 n = in.n;
-  if (n == 0) {
-    fill_u64(c, dcounts, 1, 0);
-    return;
-  }
-  u32 *flags = (u32 *)S.get(n * 4);
-  hipLaunchKernelGGL(k_head_flags, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     in.keys, kw, in.vals, vb, in.times, perm, flags, n, 1);
-  u32 *gid = (u32 *)S.get(n * 4);
-  inclusive_scan_u32(c, flags, gid, n);
-  u32 *starts = (u32 *)S.get(n * 4);
-  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     flags, gid, starts, n);
-  // wrapping inclusive prefix of permuted diffs
-  u64 *pdiff = (u64 *)S.get(n * 8);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     (const u64 *)in.diffs, perm, pdiff, n);
-  u64 *pref = (u64 *)S.get(n * 8);
-  inclusive_scan_u64(c, pdiff, pref, n);
-  i64 *gsum = (i64 *)S.get(n * 8);
-  u32 *nz = (u32 *)S.get((n + 1) * 4);
-  hipLaunchKernelGGL(k_group_sums, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     starts, gid, n, pref, gsum, nz);
-  u32 *nzpos = (u32 *)S.get((n + 1) * 4);
-  exclusive_scan_u32_ns(c, nz, nzpos, n);
-  hipLaunchKernelGGL(k_emit_consolidated, dim3(ngrid(n)), dim3(BLK), 0,
-                     c->stream, in.keys, kw, in.vals, vb, in.times, perm,
-                     starts, gsum, nz, nzpos, gid, n, okeys, ovals, otimes,
-                     odiffs, dcounts);
+  consolidate_with_perm(c, kw, vb, in, perm, o, dcounts);
 }
 
 // Synchronous wrapper (ABI-level mz_gpu_consolidate and the consolidated
 // probe outputs): returns owned capacity-sized arrays + the exact count.
-void consolidate_dev(Ctx *c, u32 kw, u32 vb, DevUpdates in, u64 **okeys,
-                     u8 **ovals, u64 **otimes, i64 **odiffs, u64 *out_n) {
-  auto &S = (*c->scr);
-  u64 n = in.n;
-  u64 capn = std::max<u64>(n, 1);
-  *okeys = dnew<u64>(c, capn * kw);
-  *ovals = (u8 *)dmalloc(c, std::max<u64>(capn * vb, 1));
-  *otimes = dnew<u64>(c, capn);
-  *odiffs = dnew<i64>(c, capn);
-  u64 *dcounts = (u64 *)S.get(3 * 8);
-  consolidate_core(c, kw, vb, in, *okeys, *ovals, *otimes, *odiffs,
-                   dcounts);
-  u64 M = 0;
-  M = *(u64 *)d2h_pinned(c, dcounts, 8);
-  *out_n = M;
+FlatCols consolidate_dev(Ctx *c, u32 kw, u32 vb, DevUpdates in, u64 *out_n) {
+  FlatCols o = flat_alloc(c, in.n, kw, vb);
+  u64 *dcounts = (u64 *)(*c->scr).get(3 * 8);
+  consolidate_core(c, kw, vb, in, o, dcounts);
+  *out_n = *(u64 *)d2h_pinned(c, dcounts, 8);
+  return o;
 }
 
 // ---- keyed-table push protocol. Every operator with a
@@ -3172,13 +3133,11 @@ const u64 *corr_read(Ctx *c, const CorrBuf &b, const u64 *d_ctr, u32 n_ctr) {
 // buffer; the result, or nullptr if the push failed.
 mz_gpu_out *corr_finish(Ctx *c, CorrBuf &b, u64 emitted, bool failed) {
   DevUpdates pin{b.pk, b.pv, b.pt, b.pd, emitted};
-  u64 *ok, *ot, Mc;
-  u8 *ov;
-  i64 *od;
-  consolidate_dev(c, b.kw, b.vb, pin, &ok, &ov, &ot, &od, &Mc);
+  u64 Mc;
+  FlatCols o = consolidate_dev(c, b.kw, b.vb, pin, &Mc);
   corr_free(c, b);
-  if (!failed) return make_out(ok, ov, ot, od, Mc, b.kw, b.vb);
-  for (void *p : {(void *)ok, (void *)ov, (void *)ot, (void *)od}) dfree(c, p);
+  if (!failed) return make_out(o, Mc, b.kw, b.vb);
+  flat_free(c, o);
   return nullptr;
 }
 
@@ -3186,19 +3145,13 @@ void free_batch(Ctx *c, DevBatch &b) {
   // Batches are probed on the MAIN stream; freeing there (in-order after
   // every probe enqueued so far) is always safe, and lets lane/flush
   // paths retire batches without gating the lane on the main stream.
-  const char *names[10] = {"keys", "kv_off", "vals", "vu_off", "v_offs",
-                           "val_key", "times", "diffs", "upd_val", "hash"};
-  void *ps[10] = {(void *)b.keys, (void *)b.kv_off, (void *)b.vals,
-                  (void *)b.vu_off, (void *)b.v_offs, (void *)b.val_key,
-                  (void *)b.times, (void *)b.diffs, (void *)b.upd_val,
-                  (void *)b.hash};
   hipStream_t ps_stream = c->stream;
   if (c->main_stream) c->stream = c->main_stream;
-  for (int i = 0; i < 10; i++) {
-    if (getenv("MZ_DBG_FINI") && ps[i])
-      fprintf(stderr, "[free_batch] %s %p\n", names[i], ps[i]);
-    dfree(c, ps[i]);
-  }
+  for (void *p : {(void *)b.keys, (void *)b.kv_off, (void *)b.vals,
+                  (void *)b.vu_off, (void *)b.v_offs, (void *)b.val_key,
+                  (void *)b.times, (void *)b.diffs, (void *)b.upd_val,
+                  (void *)b.hash})
+    dfree(c, p);
   c->stream = ps_stream;
   b = DevBatch();
 }
@@ -3275,6 +3228,14 @@ DevBatch build_batch_core(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals,
   return b;
 }
 
+// Install, step one: a sealed batch's host-side counts are the three
+// dcounts words (n_upds, n_keys, n_vals) once they have been read back.
+void set_counts(DevBatch &b, const u64 *cnt) {
+  b.n_upds = cnt[0];
+  b.n_keys = cnt[1];
+  b.n_vals = cnt[2];
+}
+
 // Synchronous wrapper for sealed inputs with host-known count.
 DevBatch build_batch(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals, u64 *times,
                      i64 *diffs, u64 n, u64 lower, u64 upper) {
@@ -3288,11 +3249,91 @@ DevBatch build_batch(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals, u64 *times,
   HIP_CHECK(hipMemcpyAsync(cnt, dcounts, 3 * 8, hipMemcpyDeviceToHost,
                            c->stream));
   HIP_CHECK(hipStreamSynchronize(c->stream));
-  b.n_upds = cnt[0];
-  b.n_keys = cnt[1];
-  b.n_vals = cnt[2];
+  set_counts(b, cnt);
   return b;
 }
+
+// ---- arrangement maintenance protocol: seal, install,
+// policy. Everything here runs on the CURRENT lane (c->stream, *c->scr);
+// the callers' guards choose it.
+
+// A sealed batch before its install: the batch with its host counts still
+// unset, the device words they will be read from (lane scratch), and the
+// flat key/val columns when the caller asked to keep them (times/diffs
+// always belong to the batch).
+struct Sealed {
+  DevBatch batch;
+  u64 *dcounts = nullptr;
+  u64 *flat_keys = nullptr;
+  u8 *flat_vals = nullptr;
+};
+
+// The seal's tail, enqueue-only: consolidate `in` along a ready ordering
+// `perm` into fresh flat columns and build the batch over them. perm ==
+// nullptr sorts first (consolidate_core, with the cached plan if given —
+// the only way this can synchronise is the min/max read of an unplanned
+// sort).
+Sealed seal_ordered(Ctx *c, u32 kw, u32 vb, DevUpdates in, const u32 *perm,
+                    mz_gpu_arr::SortPlan *plan, u64 lower, u64 upper,
+                    int keep_flat) {
+  FlatCols o = flat_alloc(c, in.n, kw, vb);
+  Sealed s;
+  s.dcounts = (u64 *)(*c->scr).get(3 * 8);
+  if (perm)
+    consolidate_with_perm(c, kw, vb, in, perm, o, s.dcounts);
+  else
+    consolidate_core(c, kw, vb, in, o, s.dcounts, plan);
+  s.batch = build_batch_core(c, kw, vb, o.keys, o.vals, o.times, o.diffs,
+                             in.n, lower, upper, s.dcounts, keep_flat);
+  if (keep_flat) {
+    s.flat_keys = o.keys;
+    s.flat_vals = o.vals;
+  }
+  return s;
+}
+
+// Seal staged updates: order them (identity when the caller vouches for
+// canonical order, else the radix sort), then the tail above.
+Sealed seal_updates(Ctx *c, u32 kw, u32 vb, DevUpdates d, u64 lower,
+                    u64 upper, mz_gpu_arr::SortPlan *plan, int keep_flat) {
+  u32 *perm = nullptr;
+  if (d.sorted && d.n) {
+    // already in canonical order: skip the radix passes, identity perm
+    perm = (u32 *)(*c->scr).get(d.n * 4);
+    hipLaunchKernelGGL(k_iota, dim3(ngrid(d.n)), dim3(BLK), 0, c->stream,
+                       perm, d.n);
+  }
+  return seal_ordered(c, kw, vb, d, perm, plan, lower, upper, keep_flat);
+}
+
+// Install, step two: replace batches [from, to) with their merge. The
+// inputs are freed on the MAIN stream (free_batch), in-order after every
+// probe of them enqueued so far — no lane gating needed.
+void replace_range(Ctx *c, mz_gpu_arr *a, size_t from, size_t to,
+                   const DevBatch &merged) {
+  for (size_t i = from; i < to; i++) free_batch(c, a->batches[i]);
+  a->batches.erase(a->batches.begin() + from, a->batches.begin() + to);
+  a->batches.insert(a->batches.begin() + from, merged);
+}
+
+// What a merge of batches [from, to) covers: row total and the frontier
+// hull (lower 0 for an empty range).
+struct RangeHeader {
+  u64 total = 0, lower = 0, upper = 0;
+};
+RangeHeader range_header(const mz_gpu_arr *a, size_t from, size_t to) {
+  RangeHeader h;
+  u64 lo = UINT64_MAX;
+  for (size_t i = from; i < to; i++) {
+    h.total += a->batches[i].n_upds;
+    lo = std::min(lo, a->batches[i].lower);
+    h.upper = std::max(h.upper, a->batches[i].upper);
+  }
+  h.lower = lo == UINT64_MAX ? 0 : lo;
+  return h;
+}
+
+void merge_range_vl(Ctx *c, mz_gpu_arr *a, size_t from, size_t to);
 
 // Merge an arrangement's batches [from, to) into one (logical compaction
 // applied). Policy is the host's; semantics = concat + advance + consolidate.
@@ -3300,27 +3341,21 @@ DevBatch build_batch(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals, u64 *times,
 // a->pending_merge — the inputs stay in the batch list (probes keep
 // using them; the merged batch holds the same logical updates) until
 // merge_install replaces them at the next flush.
-// varlen merges are defined after this namespace (they reuse the varlen
-// consolidation machinery); dispatched through this hook
-void (*merge_range_vl_fn)(Ctx *, mz_gpu_arr *, size_t, size_t) = nullptr;
-
+// (Varlen merges, defined with the varlen consolidation machinery below,
+// are always synchronous.)
 void merge_range(Ctx *c, mz_gpu_arr *a, size_t from, size_t to,
                  int deferred = 0) {
   if (to - from <= 1) return;
   if (is_varlen(a->schema.vb)) {
-    merge_range_vl_fn(c, a, from, to);
+    merge_range_vl(c, a, from, to);
     return;
   }
   MZ_PROF(c, "merge_range");
   auto &S = (*c->scr);
   S.reset();
   u32 kw = a->schema.kw, vb = a->schema.vb;
-  u64 total = 0, lo = UINT64_MAX, hi = 0;
-  for (size_t i = from; i < to; i++) {
-    total += a->batches[i].n_upds;
-    lo = std::min(lo, a->batches[i].lower);
-    hi = std::max(hi, a->batches[i].upper);
-  }
+  RangeHeader h = range_header(a, from, to);
+  u64 total = h.total;
   u64 *keys = (u64 *)S.get(total * kw * 8);
   u8 *vals = (u8 *)S.get(std::max<u64>(total * vb, 1));
   u64 *times = (u64 *)S.get(total * 8);
@@ -3338,12 +3373,7 @@ void merge_range(Ctx *c, mz_gpu_arr *a, size_t from, size_t to,
     }
   }
   DevUpdates in{keys, vals, times, diffs, total};
-  u64 capn = std::max<u64>(total, 1);
-  u64 *ok = dnew<u64>(c, capn * kw);
-  u8 *ov = (u8 *)dmalloc(c, std::max<u64>(capn * vb, 1));
-  u64 *ot = dnew<u64>(c, capn);
-  i64 *od = dnew<i64>(c, capn);
-  u64 *dcounts = (u64 *)S.get(3 * 8);
+  u32 *perm = nullptr;
   if (total) {
     // All inputs are sorted runs (logical-compaction advance is monotone,
     // so expansion preserves order): a merge-path tournament over the
@@ -3352,7 +3382,7 @@ void merge_range(Ctx *c, mz_gpu_arr *a, size_t from, size_t to,
     // columnation.rs:653-713), generalized to k runs in ceil(log2 k)
     // passes. First-pass inputs are counting ranges; later passes merge
     // the sorted index arrays with the same row comparator.
-    u32 *perm = (u32 *)S.get(total * 4);
+    perm = (u32 *)S.get(total * 4);
     {
       MZ_PROF(c, "merge_path");
       RowLess cmp{keys, vals, times, kw, vb};
@@ -3421,54 +3451,43 @@ void merge_range(Ctx *c, mz_gpu_arr *a, size_t from, size_t to,
         HIP_CHECK(hipMemcpyAsync(perm, cur, total * 4,
                                  hipMemcpyDeviceToDevice, c->stream));
     }
-    {
-      MZ_PROF(c, "merge_consol_perm");
-      consolidate_with_perm(c, kw, vb, in, perm, ok, ov, ot, od, dcounts);
-    }
-  } else {
-    consolidate_core(c, kw, vb, in, ok, ov, ot, od, dcounts);
   }
-  DevBatch merged =
-      build_batch_core(c, kw, vb, ok, ov, ot, od, total,
-                       lo == UINT64_MAX ? 0 : lo, hi, dcounts);
+  // the seal's tail over the merged order (an empty range has no order
+  // and consolidates to zero rows either way)
+  Sealed s = seal_ordered(c, kw, vb, in, perm, nullptr, h.lower, h.upper, 0);
   if (deferred) {
     a->pending_merge.active = 1;
     a->pending_merge.from = from;
     a->pending_merge.to = to;
-    a->pending_merge.merged = merged;
-    HIP_CHECK(hipMemcpyAsync(a->pending_merge.cnt, dcounts, 3 * 8,
+    a->pending_merge.merged = s.batch;
+    HIP_CHECK(hipMemcpyAsync(a->pending_merge.cnt, s.dcounts, 3 * 8,
                              hipMemcpyDeviceToHost, c->stream));
     return;
   }
   u64 cnt[3] = {0, 0, 0};
-  HIP_CHECK(hipMemcpyAsync(cnt, dcounts, 3 * 8, hipMemcpyDeviceToHost,
+  HIP_CHECK(hipMemcpyAsync(cnt, s.dcounts, 3 * 8, hipMemcpyDeviceToHost,
                            c->stream));
   HIP_CHECK(hipStreamSynchronize(c->stream));
-  merged.n_upds = cnt[0];
-  merged.n_keys = cnt[1];
-  merged.n_vals = cnt[2];
-  for (size_t i = from; i < to; i++) free_batch(c, a->batches[i]);
-  a->batches.erase(a->batches.begin() + from, a->batches.begin() + to);
-  a->batches.insert(a->batches.begin() + from, merged);
+  set_counts(s.batch, cnt);
+  replace_range(c, a, from, to, s.batch);
 }
 
-// Install a deferred merge (the lane is synced by the caller): replace
-// the input range with the merged batch; the inputs' frees are gated on
-// the main stream's enqueues so far (probes that read them).
+// Install a deferred merge whose stream the caller knows to be done (its
+// counts have landed in pm.cnt): replace the input range with the merged
+// batch.
 void merge_install(Ctx *c, mz_gpu_arr *a) {
   auto &pm = a->pending_merge;
   if (!pm.active) return;
-  DevBatch merged = pm.merged;
-  merged.n_upds = pm.cnt[0];
-  merged.n_keys = pm.cnt[1];
-  merged.n_vals = pm.cnt[2];
-  // frees run on the MAIN stream (free_batch), in-order after every
-  // probe of the inputs enqueued so far — no lane gating needed
-  for (size_t i = pm.from; i < pm.to; i++) free_batch(c, a->batches[i]);
-  a->batches.erase(a->batches.begin() + pm.from,
-                   a->batches.begin() + pm.to);
-  a->batches.insert(a->batches.begin() + pm.from, merged);
+  set_counts(pm.merged, pm.cnt);
+  replace_range(c, a, pm.from, pm.to, pm.merged);
   pm.active = 0;
+}
+
+// Finish a deferred merge now: wait for its stream, then install it.
+void merge_finish(Ctx *c, mz_gpu_arr *a) {
+  if (!a->pending_merge.active) return;
+  if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
+  merge_install(c, a);
 }
 
 }  // namespace
@@ -3652,6 +3671,8 @@ __global__ void k_vl_expand_copy(DevBatch b, u32 kw, u64 frontier,
   }
 }
 
+namespace {
+
 // consolidated varlen columns (owned device arrays, exact sizes)
 struct VlCols {
   u64 *keys = nullptr;
@@ -3693,26 +3714,12 @@ VlCols consolidate_vl(Ctx *c, u32 kw, const u64 *keys, const u32 *vstarts,
   hipLaunchKernelGGL(k_vl_head_flags, dim3(ngrid(n)), dim3(BLK), 0,
                      c->stream, keys, kw, vstarts, vends, arena, times,
                      perm, flags, n, 1);
-  u32 *gid = (u32 *)S.get(n * 4);
-  inclusive_scan_u32(c, flags, gid, n);
-  u32 *starts = (u32 *)S.get(n * 4);
-  hipLaunchKernelGGL(k_group_starts, dim3(ngrid(n)), dim3(BLK), 0,
-                     c->stream, flags, gid, starts, n);
-  u64 *pdiff = (u64 *)S.get(n * 8);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     (const u64 *)diffs, perm, pdiff, n);
-  u64 *pref = (u64 *)S.get(n * 8);
-  inclusive_scan_u64(c, pdiff, pref, n);
-  i64 *gsum = (i64 *)S.get(n * 8);
-  u32 *nz = (u32 *)S.get((n + 1) * 4);
-  hipLaunchKernelGGL(k_group_sums, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     starts, gid, n, pref, gsum, nz);
-  u32 *nzpos = (u32 *)S.get((n + 1) * 4);
-  u64 M = exclusive_scan_u32(c, nz, nzpos, n);  // syncs
+  GroupSums g = group_sum_by_perm(c, flags, diffs, perm, n);
+  u64 M = *(u32 *)d2h_pinned(c, g.nzpos + n, 4);  // syncs
   u32 *lens = (u32 *)S.get((n + 1) * 4);
   hipLaunchKernelGGL(k_vl_survivor_lens, dim3(ngrid(n)), dim3(BLK), 0,
-                     c->stream, starts, gid, nz, nzpos, n, perm, vstarts,
-                     vends, lens);
+                     c->stream, g.starts, g.gid, g.nz, g.nzpos, n, perm,
+                     vstarts, vends, lens);
   u32 *ovoffs = dnew<u32>(c, M + 1);
   u64 bytes = exclusive_scan_u32(c, lens, ovoffs, M);  // syncs; [M+1]
   out.n = M;
@@ -3725,8 +3732,8 @@ VlCols consolidate_vl(Ctx *c, u32 kw, const u64 *keys, const u32 *vstarts,
   if (M)
     hipLaunchKernelGGL(k_vl_emit_consolidated, dim3(ngrid(n)), dim3(BLK),
                        0, c->stream, keys, kw, vstarts, vends, arena,
-                       times, perm, starts, gsum, nz, nzpos, gid, n,
-                       ovoffs, out.keys, out.arena, out.times, out.diffs);
+                       times, perm, g.starts, g.gsum, g.nz, g.nzpos, g.gid,
+                       n, ovoffs, out.keys, out.arena, out.times, out.diffs);
   HIP_CHECK(hipStreamSynchronize(c->stream));
   return out;
 }
@@ -3827,12 +3834,8 @@ void merge_range_vl(Ctx *c, mz_gpu_arr *a, size_t from, size_t to) {
   auto &S = (*c->scr);
   S.reset();
   u32 kw = a->schema.kw;
-  u64 total = 0, lo = UINT64_MAX, hi = 0;
-  for (size_t i = from; i < to; i++) {
-    total += a->batches[i].n_upds;
-    lo = std::min(lo, a->batches[i].lower);
-    hi = std::max(hi, a->batches[i].upper);
-  }
+  RangeHeader h = range_header(a, from, to);
+  u64 total = h.total;
   u64 capn = std::max<u64>(total, 1);
   u64 *keys = (u64 *)S.get(capn * kw * 8);
   u32 *lens = (u32 *)S.get((capn + 1) * 4);
@@ -3861,18 +3864,12 @@ void merge_range_vl(Ctx *c, mz_gpu_arr *a, size_t from, size_t to) {
   }
   VlCols cc = consolidate_vl(c, kw, keys, voffs, voffs + 1, arena, times,
                              diffs, total);
-  DevBatch merged = build_batch_vl(c, kw, std::move(cc),
-                                   lo == UINT64_MAX ? 0 : lo, hi);
+  DevBatch merged = build_batch_vl(c, kw, std::move(cc), h.lower, h.upper);
   HIP_CHECK(hipStreamSynchronize(c->stream));
-  for (size_t i = from; i < to; i++) free_batch(c, a->batches[i]);
-  a->batches.erase(a->batches.begin() + from, a->batches.begin() + to);
-  a->batches.insert(a->batches.begin() + from, merged);
+  replace_range(c, a, from, to, merged);
 }
 
-static const bool _mrvl_registered = [] {
-  merge_range_vl_fn = merge_range_vl;
-  return true;
-}();
+}  // namespace
 
 // Varlen probe: one thread per (delta row, batch); counts rows AND arena
 // bytes, reserves both queues per wave, emits key fields + passthrough
@@ -4021,10 +4018,7 @@ static void build_probe_batchlist(Ctx *ctx, mz_gpu_arr *a, u64 delta_lower,
       bl.b[bl.n++] = b;
     }
     if (fits) return;
-    if (a->pending_merge.active) {
-      if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
-      merge_install(ctx, a);
-    }
+    merge_finish(ctx, a);
     merge_range(ctx, a, 0, a->batches.size());
   }
 }
@@ -4132,18 +4126,16 @@ static ProbeCounts run_probe(Ctx *ctx, Queue &pq, u64 cap, u64 cap2,
 // the reference (linear_join.rs:516-541) — free the raw columns, attach.
 static void attach_err_stream(Ctx *ctx, mz_gpu_out *out, ProbeQueue &pq,
                               u64 E) {
-  u64 *cek = nullptr, *cet = nullptr;
-  i64 *ced = nullptr;
+  FlatCols ce;
   u64 Ec = 0;
   if (E) {
     DevUpdates epin{pq.q.ecodes, nullptr, pq.q.etimes, pq.q.ediffs, E};
-    u8 *unused_v;
-    consolidate_dev(ctx, 1, 0, epin, &cek, &unused_v, &cet, &ced, &Ec);
+    ce = consolidate_dev(ctx, 1, 0, epin, &Ec);
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    dfree(ctx, unused_v);
+    dfree(ctx, ce.vals);  // codes are the key column; no vals
   }
   pq.free_errs(ctx);
-  out_attach_errs(out, cek, cet, ced, Ec);
+  out_attach_errs(out, ce.keys, ce.times, ce.diffs, Ec);
 }
 
 // varlen probe host path (halfjoin / linear join over a varlen lookup):
@@ -4314,44 +4306,56 @@ void mz_gpu_prof_dump(mz_gpu_ctx *c) {
   ctx->prof.cats.clear();
 }
 
+// Arrangement teardown, shared by mz_gpu_arr_drop and mz_gpu_fini. First
+// the lane and merge-stream resources (each stream is drained before it is
+// destroyed), then the device state, freed on the ctx stream.
+static void arr_release_lanes(mz_gpu_arr *a) {
+  if (a->stream) {
+    (void)hipStreamSynchronize(a->stream);
+    (void)hipStreamDestroy(a->stream);
+    (void)hipEventDestroy(a->ev_done);
+    (void)hipEventDestroy(a->ev_gate);
+    (void)hipEventDestroy(a->ev_ready);
+    if (a->lane_scr) a->lane_scr->destroy();
+    delete a->lane_scr;
+    a->stream = nullptr;
+    a->lane_scr = nullptr;
+  }
+  if (a->mstream) {
+    (void)hipStreamSynchronize(a->mstream);
+    (void)hipStreamDestroy(a->mstream);
+    (void)hipEventDestroy(a->ev_mdone);
+    if (a->merge_scr) a->merge_scr->destroy();
+    delete a->merge_scr;
+    a->mstream = nullptr;
+    a->merge_scr = nullptr;
+  }
+}
+
+static void arr_release_state(Ctx *ctx, mz_gpu_arr *a) {
+  for (auto &b : a->batches) free_batch(ctx, b);
+  a->batches.clear();
+  dfree(ctx, a->pending.flat_keys);
+  dfree(ctx, a->pending.flat_vals);
+  dfree(ctx, a->sort_plan.dev);
+  dfree(ctx, a->sort_plan.d_flag);
+  if (a->pending.active) free_batch(ctx, a->pending.batch);
+  if (a->pending_merge.active) free_batch(ctx, a->pending_merge.merged);
+}
+
 void mz_gpu_fini(mz_gpu_ctx *c) {
   if (!c) return;
   Ctx *ctx = &c->impl;
   // release everything the library owns: lane resources, arrangement
   // batches, operator state tables, scratch arenas (leaking these across
   // many short-lived contexts exhausted HBM)
-  for (mz_gpu_arr *a : ctx->arrs) {
-    if (a->stream) {
-      (void)hipStreamSynchronize(a->stream);
-      (void)hipStreamDestroy(a->stream);
-      (void)hipEventDestroy(a->ev_done);
-      (void)hipEventDestroy(a->ev_gate);
-      (void)hipEventDestroy(a->ev_ready);
-      if (a->lane_scr) a->lane_scr->destroy();
-      delete a->lane_scr;
-      a->stream = nullptr;
-    }
-    if (a->mstream) {
-      (void)hipStreamSynchronize(a->mstream);
-      (void)hipStreamDestroy(a->mstream);
-      (void)hipEventDestroy(a->ev_mdone);
-      if (a->merge_scr) a->merge_scr->destroy();
-      delete a->merge_scr;
-      a->mstream = nullptr;
-    }
-  }
+  for (mz_gpu_arr *a : ctx->arrs) arr_release_lanes(a);
   (void)hipStreamSynchronize(ctx->stream);
   const char *dbg = getenv("MZ_DBG_FINI");
   for (mz_gpu_arr *a : ctx->arrs) {
     if (dbg) fprintf(stderr, "[fini] arr %p batches=%zu\n", (void *)a,
                      a->batches.size());
-    for (auto &b : a->batches) free_batch(ctx, b);
-    dfree(ctx, a->pending.flat_keys);
-    dfree(ctx, a->pending.flat_vals);
-    dfree(ctx, a->sort_plan.dev);
-    dfree(ctx, a->sort_plan.d_flag);
-    if (a->pending.active) free_batch(ctx, a->pending.batch);
-    if (a->pending_merge.active) free_batch(ctx, a->pending_merge.merged);
+    arr_release_state(ctx, a);
     delete a;
   }
   ctx->arrs.clear();
@@ -4387,10 +4391,7 @@ const char *mz_gpu_last_error(mz_gpu_ctx *c) { return c->impl.err.c_str(); }
 int mz_gpu_sync(mz_gpu_ctx *c) {
   for (mz_gpu_arr *a : c->impl.arrs) {
     arr_flush_impl(&c->impl, a);
-    if (a->pending_merge.active) {
-      if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
-      merge_install(&c->impl, a);
-    }
+    merge_finish(&c->impl, a);
     if (a->stream) HIP_CHECK(hipStreamSynchronize(a->stream));
     if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
   }
@@ -4408,32 +4409,11 @@ mz_gpu_arr *mz_gpu_arr_create(mz_gpu_ctx *c, const mz_gpu_schema *s) {
 void mz_gpu_arr_drop(mz_gpu_ctx *c, mz_gpu_arr *a) {
   Ctx *ctx = &c->impl;
   arr_flush_impl(ctx, a);
-  if (a->pending_merge.active) {  // in-flight deferred merge reads batches
-    if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
-    merge_install(ctx, a);
-  }
-  if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto &b : a->batches) free_batch(ctx, b);
-  a->batches.clear();
-  // full teardown: lane resources, registry entry, the struct itself
-  if (a->stream) {
-    (void)hipStreamDestroy(a->stream);
-    (void)hipEventDestroy(a->ev_done);
-    (void)hipEventDestroy(a->ev_gate);
-    (void)hipEventDestroy(a->ev_ready);
-    if (a->lane_scr) a->lane_scr->destroy();
-    delete a->lane_scr;
-    a->stream = nullptr;
-    a->lane_scr = nullptr;
-  }
-  if (a->mstream) {
-    (void)hipStreamSynchronize(a->mstream);
-    (void)hipStreamDestroy(a->mstream);
-    (void)hipEventDestroy(a->ev_mdone);
-    if (a->merge_scr) a->merge_scr->destroy();
-    delete a->merge_scr;
-    a->mstream = nullptr;
-  }
+  merge_finish(ctx, a);  // an in-flight deferred merge reads the batches
+  // full teardown: lane resources, device state, registry entry, the
+  // struct itself
+  arr_release_lanes(a);
+  arr_release_state(ctx, a);
   auto &v = ctx->arrs;
   v.erase(std::remove(v.begin(), v.end(), a), v.end());
   delete a;
@@ -4444,101 +4424,105 @@ void mz_gpu_arr_drop(mz_gpu_ctx *c, mz_gpu_arr *a) {
 // keep batch sizes decreasing by >=2x tail-to-head; merging the tail
 // whenever the invariant breaks costs O(log) amortized merge work per
 // update and keeps the probe fan-out at ~log(arrangement/batch).
-// Deferred variant: enqueue at most ONE merge (the innermost due) per
-// call; cascades progress one merge per flush, off the probe critical
-// path. The 10-batch hard cap stays synchronous (probe BatchList bound).
-// Adaptive small-batch pool depth (A/B-measured on the final build):
-// probing costs ~64 B/delta-row per pooled batch, merging costs one
-// k-way rewrite per cycle. Small per-step batches amortize merges best
-// with a DEEP pool (100k rows: pool 8 beat 6 by 6%); large batches pay
-// more for probe fan-out than merges, so a SHALLOW pool wins (1M rows:
-// pool 4 beat 6 by 22%). MZ_GPU_SMALL_POOL pins a fixed depth.
-static long pool_depth(long env_pool, const mz_gpu_arr *a) {
-  if (env_pool >= 0) return env_pool;
-  u64 last = a->batches.empty() ? 0 : a->batches.back().n_upds;
-  if (last >= (512u << 10)) return 4;
-  if (last <= (256u << 10)) return 8;
-  return 6;
-}
-
-static void spine_policy_deferred(Ctx *ctx, mz_gpu_arr *a) {
-  static const u64 SMALL = [] {
-    const char *e = getenv("MZ_GPU_SMALL");
-    return e ? (u64)atoll(e) : (u64)(4u << 20);
-  }();
-  static const long POOL = [] {
-    const char *e = getenv("MZ_GPU_SMALL_POOL");
-    return e ? atol(e) : -1;  // -1 = adaptive on batch size
-  }();
-  static const double GEO = [] {
-    const char *e = getenv("MZ_GPU_GEO");
-    return e ? atof(e) : 1.0;
-  }();
-  if (a->pending_merge.active) return;  // one in flight per arrangement
-  size_t nb = a->batches.size();
-  if (nb >= 2 &&
-      (double)a->batches[nb - 2].n_upds <=
-          GEO * (double)a->batches[nb - 1].n_upds &&
-      a->batches[nb - 2].n_upds + a->batches[nb - 1].n_upds >= SMALL) {
-    MergeGuard mg(ctx, a);
-    merge_range(ctx, a, nb - 2, nb, 1);
-    return;
-  }
-  size_t i = nb;
-  while (i > 0 && a->batches[i - 1].n_upds < SMALL) i--;
-  if ((long)(nb - i) > pool_depth(POOL, a)) {
-    MergeGuard mg(ctx, a);
-    merge_range(ctx, a, i, nb, 1);
-    return;
-  }
-  while (a->batches.size() > 10)  // hard cap: synchronous catch-up
-    merge_range(ctx, a, 0, a->batches.size());
-}
-
-static void spine_policy(Ctx *ctx, mz_gpu_arr *a) {
-  // Large batches keep the geometric pair rule (merge-path pair merges
-  // are O(n)); small batches pool lazily and merge k-way when the pool
-  // exceeds 6 — per-merge fixed overhead (~25 kernel launches + syncs)
-  // made per-step pair merges of 100k-row batches the dominant step cost.
-  // 4M default: measured 2x on the 1M-row churn config (per-step pair
-  // merges of 1M batches into the resident run were the dominant cost;
-  // pooling amortizes the big merge over POOL steps).
+//
+// The knobs, read once per process at the first policy decision.
+// Large batches keep the geometric pair rule (merge-path pair merges
+// are O(n)); small batches pool lazily and merge k-way when the pool
+// exceeds its depth — per-merge fixed overhead (~25 kernel launches +
+// syncs) made per-step pair merges of 100k-row batches the dominant step
+// cost.
+struct SpineKnobs {
+  // MZ_GPU_SMALL, 4M default: measured 2x on the 1M-row churn config
+  // (per-step pair merges of 1M batches into the resident run were the
+  // dominant cost; pooling amortizes the big merge over POOL steps).
   // 4M/6 defaults: measured best at honest steady state (20-step runs
   // spanning full pool cycles: 4.06 ms/step vs 12.6 at 8M/8 — deep pools
   // inflate probe fan-out and the amortized big-run rewrite; per-step
   // pair merges without pooling ran 10+ ms/step).
-  static const u64 SMALL = [] {
-    const char *e = getenv("MZ_GPU_SMALL");
-    return e ? (u64)atoll(e) : (u64)(4u << 20);
-  }();
-  static const long POOL = [] {
-    const char *e = getenv("MZ_GPU_SMALL_POOL");
-    return e ? atol(e) : -1;  // -1 = adaptive on batch size
-  }();
-  // GEO=1.0: merge the run below only once the new run matches its
+  u64 small;
+  // MZ_GPU_SMALL_POOL pins a fixed pool depth; -1 = adaptive on batch
+  // size (A/B-measured on the final build): probing costs ~64 B/delta-row
+  // per pooled batch, merging costs one k-way rewrite per cycle. Small
+  // per-step batches amortize merges best with a DEEP pool (100k rows:
+  // pool 8 beat 6 by 6%); large batches pay more for probe fan-out than
+  // merges, so a SHALLOW pool wins (1M rows: pool 4 beat 6 by 22%).
+  long pool;
+  // MZ_GPU_GEO=1.0: merge the run below only once the new run matches its
   // size (tiering-leaning). The leveling factor 2.0 re-rewrote the big
   // resident run on a cascade every ~30 steps: 109+184ms giant-merge
   // steps vs 51ms at 1.0 (12.1 -> 5.6 ms/step avg over 36-step windows).
-  static const double GEO = [] {
-    const char *e = getenv("MZ_GPU_GEO");
-    return e ? atof(e) : 1.0;
+  double geo;
+};
+static const SpineKnobs &spine_knobs() {
+  static const SpineKnobs K = [] {
+    const char *s = getenv("MZ_GPU_SMALL");
+    const char *p = getenv("MZ_GPU_SMALL_POOL");
+    const char *g = getenv("MZ_GPU_GEO");
+    return SpineKnobs{s ? (u64)atoll(s) : (u64)(4u << 20), p ? atol(p) : -1,
+                      g ? atof(g) : 1.0};
   }();
-  for (;;) {
-    size_t nb = a->batches.size();
-    if (nb >= 2 &&
-        (double)a->batches[nb - 2].n_upds <=
-            GEO * (double)a->batches[nb - 1].n_upds &&
-        a->batches[nb - 2].n_upds + a->batches[nb - 1].n_upds >= SMALL)
-      merge_range(ctx, a, nb - 2, nb);
-    else
+  return K;
+}
+
+// One policy decision over the batch sizes: the range [from, to) the given
+// rule wants merged now, or from == to for none.
+enum SpineRule { RULE_PAIR, RULE_POOL, RULE_CAP };
+struct MergeDue {
+  size_t from = 0, to = 0;
+  explicit operator bool() const { return to > from; }
+};
+static MergeDue spine_due(const mz_gpu_arr *a, SpineRule rule) {
+  const SpineKnobs &K = spine_knobs();
+  const auto &B = a->batches;
+  size_t nb = B.size();
+  switch (rule) {
+    case RULE_PAIR:  // the last run has caught up with the one below it
+      if (nb >= 2 &&
+          (double)B[nb - 2].n_upds <= K.geo * (double)B[nb - 1].n_upds &&
+          B[nb - 2].n_upds + B[nb - 1].n_upds >= K.small)
+        return {nb - 2, nb};
+      break;
+    case RULE_POOL: {  // the trailing small batches outgrew the pool
+      size_t i = nb;
+      while (i > 0 && B[i - 1].n_upds < K.small) i--;
+      long depth = K.pool;
+      if (depth < 0) {
+        u64 last = B.empty() ? 0 : B.back().n_upds;
+        depth = last >= (512u << 10) ? 4 : last <= (256u << 10) ? 8 : 6;
+      }
+      if ((long)(nb - i) > depth) return {i, nb};
+      break;
+    }
+    case RULE_CAP:  // hard cap: the probe BatchList's capacity
+      if (nb > 10) return {0, nb};
       break;
   }
-  size_t nb = a->batches.size();
-  size_t i = nb;
-  while (i > 0 && a->batches[i - 1].n_upds < SMALL) i--;
-  if ((long)(nb - i) > pool_depth(POOL, a)) merge_range(ctx, a, i, nb);
-  while (a->batches.size() > 10)  // hard cap (probe BatchList capacity)
-    merge_range(ctx, a, 0, a->batches.size());
+  return {};
+}
+
+// Synchronous driver: the pair rule until it rests, the pool rule once,
+// then the cap.
+static void spine_policy(Ctx *ctx, mz_gpu_arr *a) {
+  while (MergeDue m = spine_due(a, RULE_PAIR))
+    merge_range(ctx, a, m.from, m.to);
+  if (MergeDue m = spine_due(a, RULE_POOL)) merge_range(ctx, a, m.from, m.to);
+  while (MergeDue m = spine_due(a, RULE_CAP))
+    merge_range(ctx, a, m.from, m.to);
+}
+
+// Deferred driver: enqueue at most ONE merge (the innermost due) per call
+// on the merge stream; cascades progress one merge per flush, off the
+// probe critical path. The hard cap stays synchronous.
+static void spine_policy_deferred(Ctx *ctx, mz_gpu_arr *a) {
+  if (a->pending_merge.active) return;  // one in flight per arrangement
+  for (SpineRule rule : {RULE_PAIR, RULE_POOL})
+    if (MergeDue m = spine_due(a, rule)) {
+      MergeGuard mg(ctx, a);
+      merge_range(ctx, a, m.from, m.to, 1);
+      return;
+    }
+  while (MergeDue m = spine_due(a, RULE_CAP))
+    merge_range(ctx, a, m.from, m.to);
 }
 
 int mz_gpu_arr_push_batch(mz_gpu_ctx *c, mz_gpu_arr *a,
@@ -4554,24 +4538,20 @@ int mz_gpu_arr_push_batch(mz_gpu_ctx *c, mz_gpu_arr *a,
   u32 kw = a->schema.kw, vb = a->schema.vb;
   DevUpdates d = stage_updates(ctx, u, kw, vb);
   // copy into owned arrays (batch owns its storage)
-  u64 *keys = dnew<u64>(ctx, std::max<u64>(d.n, 1) * kw);
-  u8 *vals = (u8 *)dmalloc(ctx, std::max<u64>(d.n * vb, 1));
-  u64 *times = dnew<u64>(ctx, std::max<u64>(d.n, 1));
-  i64 *diffs = dnew<i64>(ctx, std::max<u64>(d.n, 1));
+  FlatCols f = flat_alloc(ctx, d.n, kw, vb);
   if (d.n) {
-    HIP_CHECK(hipMemcpyAsync(keys, d.keys, d.n * kw * 8,
+    HIP_CHECK(hipMemcpyAsync(f.keys, d.keys, d.n * kw * 8,
                              hipMemcpyDeviceToDevice, ctx->stream));
     if (vb)
-      HIP_CHECK(hipMemcpyAsync(vals, d.vals, d.n * vb,
+      HIP_CHECK(hipMemcpyAsync(f.vals, d.vals, d.n * vb,
                                hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(times, d.times, d.n * 8,
+    HIP_CHECK(hipMemcpyAsync(f.times, d.times, d.n * 8,
                              hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(diffs, d.diffs, d.n * 8,
+    HIP_CHECK(hipMemcpyAsync(f.diffs, d.diffs, d.n * 8,
                              hipMemcpyDeviceToDevice, ctx->stream));
   }
-  DevBatch b =
-      build_batch(ctx, kw, vb, keys, vals, times, diffs, d.n, u->lower,
-                  u->upper);
+  DevBatch b = build_batch(ctx, kw, vb, f.keys, f.vals, f.times, f.diffs,
+                           d.n, u->lower, u->upper);
   a->batches.push_back(b);
   a->upper = std::max(a->upper, u->upper);
   spine_policy(ctx, a);
@@ -4579,46 +4559,21 @@ int mz_gpu_arr_push_batch(mz_gpu_ctx *c, mz_gpu_arr *a,
   return 0;
 }
 
-// Consolidate raw updates + build + push, in one call (no intermediate
-// out-batch, copies, or extra syncs).
-// consolidate + build + push over already-staged device updates; returns
-// a pointer to the pushed batch (valid until the next spine merge).
+// Seal + install + policy over already-staged device updates, on the
+// current lane, with one sync (the counts read); returns a pointer to the
+// pushed batch (valid until the next spine merge).
 static DevBatch *arr_insert_dev(Ctx *ctx, mz_gpu_arr *a, DevUpdates d,
                                 u64 lower, u64 upper) {
   MZ_PROF(ctx, "arr_insert");
-  auto &S = (*ctx->scr);
-  u32 kw = a->schema.kw, vb = a->schema.vb;
-  u64 capn = std::max<u64>(d.n, 1);
-  u64 *ok = dnew<u64>(ctx, capn * kw);
-  u8 *ov = (u8 *)dmalloc(ctx, std::max<u64>(capn * vb, 1));
-  u64 *ot = dnew<u64>(ctx, capn);
-  i64 *od = dnew<i64>(ctx, capn);
-  u64 *dcounts = (u64 *)S.get(3 * 8);
-  if (d.sorted && d.n) {
-    // already in canonical order: skip the radix passes, identity perm
-    u32 *perm = (u32 *)S.get(d.n * 4);
-    hipLaunchKernelGGL(k_iota, dim3(ngrid(d.n)), dim3(BLK), 0, ctx->stream,
-                       perm, d.n);
-    consolidate_with_perm(ctx, kw, vb, d, perm, ok, ov, ot, od, dcounts);
-  } else {
-    consolidate_core(ctx, kw, vb, d, ok, ov, ot, od, dcounts);
-  }
-  DevBatch b = build_batch_core(ctx, kw, vb, ok, ov, ot, od, d.n, lower,
-                                upper, dcounts);
-  u64 *cnt = (u64 *)d2h_pinned(ctx, dcounts, 3 * 8);
-  b.n_upds = cnt[0];
-  b.n_keys = cnt[1];
-  b.n_vals = cnt[2];
-  a->batches.push_back(b);
+  Sealed s = seal_updates(ctx, a->schema.kw, a->schema.vb, d, lower, upper,
+                          nullptr, 0);
+  set_counts(s.batch, (u64 *)d2h_pinned(ctx, s.dcounts, 3 * 8));
+  a->batches.push_back(s.batch);
   a->upper = std::max(a->upper, upper);
   spine_policy(ctx, a);
   return &a->batches.back();
 }
 
-// Enqueue-only half of an insert: consolidate + build run on the
-// arrangement's own lane; the counts readback is issued asynchronously
-// and the sealed batch joins the spine at mz_gpu_arr_flush. Independent
-// arrangements' inserts overlap this way (one per GPU stream).
 // varlen insert: synchronous consolidate + build + push (no lane
 // pipeline — varlen is off the benchmark hot path)
 static void arr_insert_vl(Ctx *ctx, mz_gpu_arr *a,
@@ -4637,7 +4592,10 @@ static void arr_insert_vl(Ctx *ctx, mz_gpu_arr *a,
   if (a->stream) (void)hipEventRecord(a->ev_ready, a->stream);
 }
 
-// The enqueue-only insert body. `plan` non-null (device inputs only)
+// Enqueue-only half of an insert: the seal runs on the arrangement's own
+// lane; the counts readback is issued asynchronously and the sealed batch
+// joins the spine at mz_gpu_arr_flush. Independent arrangements' inserts
+// overlap this way (one per GPU stream). `plan` non-null (device inputs only)
 // uses the arrangement's cached sort plan without the minmax sync; the
 // device validity flag is copied back with the counts and checked at
 // the flush, which rebuilds synchronously on a mismatch (rare: the
@@ -4647,34 +4605,18 @@ static void insert_pipeline(Ctx *ctx, mz_gpu_arr *a, DevUpdates d,
                             mz_gpu_arr::SortPlan *plan) {
   // NOTE: does NOT reset the lane scratch — host-input callers staged
   // `d` into it (arr_insert_async_impl resets before staging)
-  auto &S = (*ctx->scr);
-  u32 kw = a->schema.kw, vb = a->schema.vb;
   if (plan && plan->d_flag) fill_u32(ctx, plan->d_flag, 1, 0);
-  u64 capn = std::max<u64>(d.n, 1);
-  u64 *ok = dnew<u64>(ctx, capn * kw);
-  u8 *ov = (u8 *)dmalloc(ctx, std::max<u64>(capn * vb, 1));
-  u64 *ot = dnew<u64>(ctx, capn);
-  i64 *od = dnew<i64>(ctx, capn);
-  u64 *dcounts = (u64 *)S.get(3 * 8);
-  if (d.sorted && d.n) {
-    u32 *perm = (u32 *)S.get(d.n * 4);
-    hipLaunchKernelGGL(k_iota, dim3(ngrid(d.n)), dim3(BLK), 0, ctx->stream,
-                       perm, d.n);
-    consolidate_with_perm(ctx, kw, vb, d, perm, ok, ov, ot, od, dcounts);
-  } else {
-    consolidate_core(ctx, kw, vb, d, ok, ov, ot, od, dcounts, plan);
-  }
-  DevBatch b = build_batch_core(ctx, kw, vb, ok, ov, ot, od, d.n, lower,
-                                upper, dcounts, /*keep_flat=*/1);
+  Sealed s = seal_updates(ctx, a->schema.kw, a->schema.vb, d, lower, upper,
+                          plan, /*keep_flat=*/1);
   a->pending.active = 1;
-  a->pending.batch = b;
+  a->pending.batch = s.batch;
   a->pending.staged = d;
   a->pending.lower = lower;
   a->pending.upper = upper;
-  a->pending.flat_keys = ok;
-  a->pending.flat_vals = ov;
+  a->pending.flat_keys = s.flat_keys;
+  a->pending.flat_vals = s.flat_vals;
   a->pending.flag[0] = 0;
-  HIP_CHECK(hipMemcpyAsync(a->pending.cnt, dcounts, 3 * 8,
+  HIP_CHECK(hipMemcpyAsync(a->pending.cnt, s.dcounts, 3 * 8,
                            hipMemcpyDeviceToHost, ctx->stream));
   if (plan && plan->d_flag)
     HIP_CHECK(hipMemcpyAsync(a->pending.flag, plan->d_flag, 4,
@@ -4738,9 +4680,7 @@ static void arr_flush_take_impl(Ctx *ctx, mz_gpu_arr *a,
     merge_install(ctx, a);
   if (a->pending.active) {
     DevBatch b = a->pending.batch;
-    b.n_upds = a->pending.cnt[0];
-    b.n_keys = a->pending.cnt[1];
-    b.n_vals = a->pending.cnt[2];
+    set_counts(b, a->pending.cnt);
     a->batches.push_back(b);
     a->upper = std::max(a->upper, a->pending.upper);
     a->pending.active = 0;
@@ -4837,10 +4777,7 @@ int mz_gpu_arr_maintain(mz_gpu_ctx *c, mz_gpu_arr *a, uint64_t fuel) {
   Ctx *ctx = &c->impl;
   arr_flush_impl(ctx, a);  // pending insert joins; pending merge installs
   LaneGuard lane(ctx, a);
-  if (a->pending_merge.active) {  // flush's policy may have enqueued one
-    if (a->mstream) HIP_CHECK(hipStreamSynchronize(a->mstream));
-    merge_install(ctx, a);
-  }
+  merge_finish(ctx, a);  // the flush's policy may have enqueued one
   merge_range(ctx, a, 0, a->batches.size());
   return 0;
 }
@@ -4935,14 +4872,10 @@ int mz_gpu_consolidate(mz_gpu_ctx *c, const mz_gpu_schema *s,
                        cc.n, cc.bytes, kw);
     return 0;
   }
-  u64 *ok;
-  u8 *ov;
-  u64 *ot;
-  i64 *od;
   u64 M;
-  consolidate_dev(ctx, kw, vb, d, &ok, &ov, &ot, &od, &M);
+  FlatCols o = consolidate_dev(ctx, kw, vb, d, &M);
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  *out = make_out(ok, ov, ot, od, M, kw, vb);
+  *out = make_out(o, M, kw, vb);
   return 0;
 }
 
@@ -5059,15 +4992,11 @@ static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
                     okw, ovb);
   } else {
     DevUpdates pin{pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M};
-    u64 *ok;
-    u8 *ov;
-    u64 *ot;
-    i64 *od;
     u64 Mc;
-    consolidate_dev(ctx, okw, ovb, pin, &ok, &ov, &ot, &od, &Mc);
+    FlatCols o = consolidate_dev(ctx, okw, ovb, pin, &Mc);
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     pq.free_ok(ctx);
-    *out = make_out(ok, ov, ot, od, Mc, okw, ovb);
+    *out = make_out(o, Mc, okw, ovb);
   }
   attach_err_stream(ctx, *out, pq, r.E);
   return 0;
@@ -5673,18 +5602,14 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
         base += m2;
       }
       DevUpdates pin{ck2, cv2, ct2, cd2, total};
-      u64 *ok;
-      u8 *ov;
-      u64 *ot;
-      i64 *od;
       u64 Mc;
-      consolidate_dev(ctx, kw, vb, pin, &ok, &ov, &ot, &od, &Mc);
+      FlatCols o = consolidate_dev(ctx, kw, vb, pin, &Mc);
       HIP_CHECK(hipMemcpyAsync(&errflag, op->d_err, 8,
                                hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
       for (void *p : {(void *)ck2, (void *)cv2, (void *)ct2, (void *)cd2})
         dfree(ctx, p);
-      if (!errflag) *out = make_out(ok, ov, ot, od, Mc, kw, vb);
+      if (!errflag) *out = make_out(o, Mc, kw, vb);
     }
   }
   for (auto &sg : segs)
@@ -5966,16 +5891,12 @@ static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
     }
   }
   // consolidate the top-level corrections
-  u64 *ok;
-  u8 *ov;
-  u64 *ot;
-  i64 *od;
   u64 Mc = 0;
   DevUpdates fin{fk, fv, ft, fd, fM};
-  consolidate_dev(ctx, kw, 8, fin, &ok, &ov, &ot, &od, &Mc);
+  FlatCols o = consolidate_dev(ctx, kw, 8, fin, &Mc);
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   for (void *p : owned) dfree(ctx, p);
-  *out = make_out(ok, ov, ot, od, Mc, kw, 8);
+  *out = make_out(o, Mc, kw, 8);
   return 0;
 }
 
