@@ -516,6 +516,35 @@ void mz_gpu_collation_drop(mz_gpu_ctx *ctx, mz_gpu_collation *op);
 int  mz_gpu_peek(mz_gpu_ctx *ctx, mz_gpu_arr *arr, const uint64_t *keys,
                  uint64_t n_keys, uint64_t time, mz_gpu_out **out);
 
+/* Full-scan peek (IndexPeek with no literal constraints, compute_state.rs):
+ * every (key, val) of the arrangement with its diffs at t' <= as_of summed,
+ * passed through `mfp` (NULL = identity), consolidated. Out rows:
+ * (key, val, as_of, diff) in canonical order, the format mz_gpu_peek
+ * returns; rows whose mfp evaluation errors land in the out-batch's error
+ * stream as (MZ_ERR_DIVISION_BY_ZERO, as_of, summed diff).
+ * `mfp` is a closure over (MZ_SRC_KEY, MZ_SRC_VAL_LOOKUP = the stored val):
+ * filters, a projection, computed fields. The reference fails a peek that
+ * meets a negative net count ("saw retractions ... for row that does not
+ * exist"); so does this call unless `allow_negative` is set, in which case
+ * such rows are returned as they are.
+ * An as_of at or beyond the arrangement's upper is legal and answers over
+ * what is installed: waiting for the frontier is the caller's, as with
+ * mz_gpu_peek. A pending mz_gpu_arr_insert_async batch whose lower bound is
+ * beyond as_of is not waited for.
+ * Errors (non-zero return, nothing allocated is kept): a varlen
+ * arrangement; an mfp that reads MZ_SRC_VAL_STREAM, that reads past the
+ * arrangement's key words or val bytes, or whose field widths do not add
+ * up to its `out` schema (a computed field is 8 bytes); as_of
+ * before the logical compaction frontier (times below it may already have
+ * been advanced to it — the reference refuses peeks before `since`); a
+ * negative net count without `allow_negative`.
+ * Not provided: ORDER BY / LIMIT finishing (the caller's, as the
+ * reference's RowSetFinishing is applied outside the index walk) and
+ * key-range bounds. */
+int  mz_gpu_peek_scan(mz_gpu_ctx *ctx, mz_gpu_arr *arr, uint64_t as_of,
+                      const mz_gpu_closure *mfp, int allow_negative,
+                      mz_gpu_out **out);
+
 /* The routing hash itself (host helper; device code uses the same). */
 uint64_t mz_gpu_route_hash(const uint64_t *key_words, uint32_t n_words);
 

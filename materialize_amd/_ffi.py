@@ -144,6 +144,9 @@ def load():
     lib.mz_gpu_peek.argtypes = [C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_uint64), C.c_uint64,
                                 C.c_uint64, C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_peek_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.POINTER(Closure), C.c_int,
+                                     C.POINTER(C.POINTER(OutBatch))]
     lib.mz_gpu_route_hash.restype = C.c_uint64
     lib.mz_gpu_route_hash.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
     lib.mz_gpu_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -161,6 +164,9 @@ class GpuCtx:
     # COUNT/SUM(DISTINCT x) (Aggregate.distinct) is implemented here; the
     # render layer refuses such plans on contexts that do not say so.
     supports_distinct_aggs = True
+    # Full-scan peeks (mz_gpu_peek_scan) are implemented here; render_peek
+    # refuses contexts that do not say so.
+    supports_scan_peek = True
 
     def __init__(self, device=0):
         self.lib = load()
@@ -394,6 +400,22 @@ class GpuCtx:
             len(keys) // kw, time, C.byref(outp)))
         return self._take(outp)
 
+    def _peek_scan(self, arr, as_of, mfp, allow_negative):
+        outp = C.POINTER(OutBatch)()
+        self._check(self.lib.mz_gpu_peek_scan(
+            self.ctx, arr, as_of,
+            C.byref(mfp) if mfp is not None else None,
+            1 if allow_negative else 0, C.byref(outp)))
+        return outp
+
+    def peek_scan(self, arr, as_of, mfp=None, allow_negative=False):
+        """Read the whole arrangement as of `as_of`: every (key, val) with
+        its diffs at t' <= as_of summed, through the closure `mfp` (None =
+        identity), consolidated. Host columns like `peek`; rows whose mfp
+        evaluation errors land in self.last_errs. A negative net count
+        raises MzGpuError unless `allow_negative`."""
+        return self._take(self._peek_scan(arr, as_of, mfp, allow_negative))
+
     # --- device-resident variants (outputs stay on the GPU; used by the
     # render layer to chain stages without host round trips) ---
     def _dev_out(self, outp, sorted=False):
@@ -424,6 +446,11 @@ class GpuCtx:
         self._check(self.lib.mz_gpu_consolidate(self.ctx, C.byref(sch),
                                                 C.byref(upd), C.byref(outp)))
         return self._dev_out(outp, sorted=True)
+
+    def peek_scan_dev(self, arr, as_of, mfp=None, allow_negative=False):
+        # consolidated output in canonical order
+        return self._dev_out(
+            self._peek_scan(arr, as_of, mfp, allow_negative), sorted=True)
 
     def halfjoin_dev(self, lookup, upd, stream_vb, le, cl):
         # raw (unconsolidated) output: the render layer's consumers —

@@ -771,6 +771,79 @@ __global__ void k_probe_walk(DeltaView d, u32 lvb, BatchList bl, int mode,
   }
 }
 
+// Full-scan peek walk (IndexPeek without literal constraints,
+// compute_state.rs): the batches are walked, not hashed into. One work
+// item per (batch, val index j) over the whole BatchList; vbase.v[b] is the
+// first item of batch b (vbase.v[bl.n] = the total), so an item finds its
+// batch by a linear search of at most 12 entries. The item's updates at
+// t' <= as_of are summed (wrapping) and ONE row per val leaves with time
+// as_of and that sum — the host consolidates across batches. Consecutive
+// lanes read consecutive val_key / vals / vu_off; keys and times/diffs are
+// near-monotone gathers. Every lane of a wave runs the same number of
+// iterations and reaches q.reserve in each (idle lanes with c = e = 0).
+struct ScanBases {
+  u64 v[13];
+};
+
+__global__ void k_scan_walk(BatchList bl, ScanBases vbase, u32 kw, u32 vb,
+                            u64 as_of, const mz_gpu_closure cl,
+                            EmitQueue q) {
+  u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  u64 total = vbase.v[bl.n];
+  u64 stride = (u64)gridDim.x * blockDim.x;
+  u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  u64 iters = (total + stride - 1) / stride;  // uniform across the wave
+  u32 lane = threadIdx.x & 63;
+  for (u64 it = 0; it < iters; it++) {
+    u64 idx = start + it * stride;
+    const u64 *key = nullptr;
+    const u8 *val = nullptr;
+    i64 s = 0;
+    int cls = 0;
+    if (idx < total) {
+      int bi = 0;
+      while (bi + 1 < bl.n && idx >= vbase.v[bi + 1]) bi++;
+      const DevBatch &b = bl.b[bi];
+      u64 j = idx - vbase.v[bi];
+      key = b.keys + (u64)b.val_key[j] * kw;
+      val = vb ? b.vals + j * vb : nullptr;
+      cls = d_closure_apply(&cl, key, nullptr, val, nullptr, nullptr);
+      if (cls) {
+        u32 lo = b.vu_off[j], hi = b.vu_off[j + 1];
+        if (bl.allpass[bi]) {
+          for (u32 u = lo; u < hi; u++) s = wadd(s, b.diffs[u]);
+        } else {
+          for (u32 u = lo; u < hi; u++)
+            if (b.times[u] <= as_of) s = wadd(s, b.diffs[u]);
+        }
+      }
+    }
+    u32 c = (cls == 1 && s != 0) ? 1u : 0u;
+    u32 e = (cls == 2 && s != 0) ? 1u : 0u;
+    u64 o, eo;
+    if (!q.reserve(c, e, lane, &o, &eo)) continue;
+    if (c) {  // count mode checked every erroring compute: this returns 1
+      (void)d_closure_apply(&cl, key, nullptr, val, q.okeys + o * okw,
+                            q.ovals + o * ovb);
+      q.otimes[o] = as_of;
+      q.odiffs[o] = s;
+    } else {
+      q.ecodes[eo] = MZ_ERR_DIVISION_BY_ZERO;
+      q.etimes[eo] = as_of;
+      q.ediffs[eo] = s;
+    }
+  }
+}
+
+// Count the negative ones among n diffs into *flag (the peek's "saw
+// retractions for a row that does not exist" check).
+__global__ void k_any_negative(const i64 *diffs, u64 n,
+                               unsigned long long *flag) {
+  GRID_STRIDE(i, n) {
+    if (diffs[i] < 0) atomicAdd(flag, 1ull);
+  }
+}
+
 // Fused two-stage delta-path probe (one delta path's two lookup stages,
 // delta_join.rs:338-472, in a single kernel): a stage-1 match produces
 // its intermediate (key2, val2) in REGISTERS and immediately probes the
@@ -5047,6 +5120,173 @@ int mz_gpu_peek(mz_gpu_ctx *c, mz_gpu_arr *arr, const uint64_t *keys,
   cl.out.key_words = kw;
   cl.out.val_bytes = vb;
   return probe_impl(&c->impl, arr, &u, 0, PM_HALF_LE, 0, &cl, 1, out);
+}
+
+// The closure shapes a full-scan peek accepts: an MFP over (key, val) —
+// the arrangement's val is the lookup side and no stream side exists.
+// Every read must stay inside the kw key words / vb val bytes.
+static const char *peek_scan_mfp_error(const mz_gpu_closure *cl, u32 kw,
+                                       u32 vb) {
+  if (cl->n_filters > MZ_GPU_MAX_FILTERS ||
+      cl->n_key_fields > MZ_GPU_MAX_FIELDS ||
+      cl->n_val_fields > MZ_GPU_MAX_FIELDS)
+    return "peek_scan: mfp filter/field count out of range";
+  if (cl->out.key_words == 0 || cl->out.key_words > (u32)MAX_KW ||
+      cl->out.val_bytes > (u32)MAX_VB)
+    return "peek_scan: mfp out schema unsupported (1..2 key words, "
+           "fixed-width val of at most 64 bytes)";
+  const char *stream = "peek_scan: mfp reads MZ_SRC_VAL_STREAM (a scan has "
+                       "no stream side)";
+  const char *past = "peek_scan: mfp reads past the arrangement's key or val";
+  // as d_cl_src resolves a source: the key, else the stored val
+  auto fits = [&](u8 src, u32 off, u32 bytes) {
+    return (u64)off + bytes <= (src == MZ_SRC_KEY ? 8ull * kw : (u64)vb);
+  };
+  for (u32 i = 0; i < cl->n_filters; i++) {
+    const mz_gpu_filter &f = cl->filters[i];
+    if (f.src == MZ_SRC_VAL_STREAM) return stream;
+    u32 w = f.width == 4 ? 4 : 8;  // d_read_int
+    if (f.src != MZ_SRC_COMPUTE) {
+      if (!fits(f.src, f.off, w)) return past;
+      continue;
+    }
+    if (f.arg0_src == MZ_SRC_VAL_STREAM || f.arg1_src == MZ_SRC_VAL_STREAM)
+      return stream;
+    if (f.off == MZ_COMPUTE_Q17_QTYLT &&  // i64; i128 sum + count at +24
+        !(fits(f.arg0_src, f.arg0, 8) && fits(f.arg1_src, f.arg1, 32)))
+      return past;
+    if (f.off == MZ_COMPUTE_CMP_FIELDS &&
+        !(fits(f.arg0_src, f.arg0, w) && fits(f.arg1_src, f.arg1, w)))
+      return past;
+  }
+  for (int which = 0; which < 2; which++) {
+    u32 nf = which ? cl->n_val_fields : cl->n_key_fields;
+    const mz_gpu_field *fs = which ? cl->val_fields : cl->key_fields;
+    u64 bytes = 0;
+    for (u32 i = 0; i < nf; i++) {
+      const mz_gpu_field &f = fs[i];
+      if (f.src == MZ_SRC_VAL_STREAM) return stream;
+      if (f.src == MZ_SRC_COMPUTE && f.off != MZ_COMPUTE_CONST0) {
+        if (f.arg0_src == MZ_SRC_VAL_STREAM ||
+            f.arg1_src == MZ_SRC_VAL_STREAM)
+          return stream;
+        if (!(fits(f.arg0_src, f.arg0, 8) && fits(f.arg1_src, f.arg1, 8)))
+          return past;
+      } else if (f.src != MZ_SRC_COMPUTE && !fits(f.src, f.off, f.width)) {
+        return past;
+      }
+      bytes += f.src == MZ_SRC_COMPUTE ? 8 : f.width;  // computes are i64
+    }
+    if (bytes != (which ? (u64)cl->out.val_bytes : 8ull * cl->out.key_words))
+      return "peek_scan: mfp field widths do not add up to its out schema";
+  }
+  return nullptr;
+}
+
+// Full-scan peek host path: the probe protocol with
+// k_scan_walk as the launch — prepare, snapshot, run_probe, consolidate,
+// negative-count check, error stream.
+static int peek_scan_impl(Ctx *ctx, mz_gpu_arr *arr, u64 as_of,
+                          const mz_gpu_closure *mfp, int allow_negative,
+                          mz_gpu_out **out) {
+  if (is_varlen(arr->schema.vb)) {
+    ctx->err = "peek_scan: varlen arrangements unsupported";
+    return 1;
+  }
+  u32 kw = arr->schema.kw, vb = arr->schema.vb;
+  mz_gpu_closure cl{};
+  if (mfp) {
+    if (const char *why = peek_scan_mfp_error(mfp, kw, vb)) {
+      ctx->err = why;
+      return 1;
+    }
+    cl = *mfp;
+  } else {  // identity: (key, val) as stored
+    cl.n_key_fields = 1;
+    cl.key_fields[0] = mz_gpu_field{MZ_SRC_KEY, 0, (u8)(8 * kw), 0, 0, 0, 0};
+    cl.n_val_fields = vb ? 1u : 0u;
+    if (vb)
+      cl.val_fields[0] =
+          mz_gpu_field{MZ_SRC_VAL_LOOKUP, 0, (u8)vb, 0, 0, 0, 0};
+    cl.out.key_words = kw;
+    cl.out.val_bytes = vb;
+  }
+  if (as_of == ~0ull) {  // as_of + 1 is the probe's exclusive bound
+    ctx->err = "peek_scan: as_of out of range";
+    return 1;
+  }
+  if (as_of < arr->logical_compaction) {
+    ctx->err = "peek_scan: as_of " + std::to_string(as_of) +
+               " is before the compaction frontier " +
+               std::to_string(arr->logical_compaction);
+    return 1;
+  }
+  u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  // a pending insert wholly beyond as_of keeps running on its lane
+  probe_prepare(ctx, arr, PM_HALF_LE, as_of + 1);
+  BatchList bl;
+  build_probe_batchlist(ctx, arr, as_of + 1, bl);
+  (*ctx->scr).reset();
+  ScanBases vbase;
+  u64 n = 0, n_upds = 0;
+  for (int b = 0; b < bl.n; b++) {
+    vbase.v[b] = n;
+    n += bl.b[b].n_vals;
+    n_upds += bl.b[b].n_upds;
+  }
+  vbase.v[bl.n] = n;
+  if (n == 0) {
+    *out = empty_out(ctx, okw, ovb);
+    return 0;
+  }
+  // One row per val at most: n is an exact bound on the ok queue, so only
+  // the error queue can overflow into the exact relaunch.
+  ProbeQueue pq{okw, ovb};
+  ProbeCounts r =
+      run_probe(ctx, pq, n, n / 4 + 1024, 2, n, [&](EmitQueue q) {
+        hipLaunchKernelGGL(k_scan_walk, dim3(ngrid(n)), dim3(BLK), 0,
+                           ctx->stream, bl, vbase, kw, vb, as_of, cl, q);
+      });
+  u64 M = r.M;
+  if (ctx->time_kernels) {  // run_probe has synced and entered the call
+    ctx->probe_batches += (u64)bl.n;
+    // Algorithmic bytes of the scan, each touched once: per val its bytes
+    // + val_key (4) + the vu_off pair (8) + its key; per update time +
+    // diff (16); the emitted rows.
+    ctx->probe_alg_bytes += n * (vb + 4ull + 8 + 8ull * kw) +
+                            n_upds * 16ull + M * (8ull * okw + ovb + 16);
+  }
+  // the same (key, val) lives in several batches, and a projecting mfp
+  // collapses distinct rows
+  DevUpdates pin{pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M};
+  u64 Mc;
+  FlatCols o = consolidate_dev(ctx, okw, ovb, pin, &Mc);
+  pq.free_ok(ctx);
+  if (!allow_negative && Mc) {
+    u64 *dneg = (u64 *)(*ctx->scr).get(8);
+    fill_u64(ctx, dneg, 1, 0);
+    hipLaunchKernelGGL(k_any_negative, dim3(ngrid(Mc)), dim3(BLK), 0,
+                       ctx->stream, o.diffs, Mc,
+                       (unsigned long long *)dneg);
+    u64 neg = *(u64 *)d2h_pinned(ctx, dneg, 8);
+    if (neg) {
+      flat_free(ctx, o);
+      pq.free_errs(ctx);
+      ctx->err = "peek_scan: negative multiplicity (" + std::to_string(neg) +
+                 " rows)";
+      return 1;
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  *out = make_out(o, Mc, okw, ovb);
+  attach_err_stream(ctx, *out, pq, r.E);
+  return 0;
+}
+
+int mz_gpu_peek_scan(mz_gpu_ctx *c, mz_gpu_arr *arr, uint64_t as_of,
+                     const mz_gpu_closure *mfp, int allow_negative,
+                     mz_gpu_out **out) {
+  return peek_scan_impl(&c->impl, arr, as_of, mfp, allow_negative, out);
 }
 
 // Raw variant: output left unconsolidated (consumer consolidates).

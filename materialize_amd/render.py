@@ -532,6 +532,77 @@ class ThresholdOp:
         return self.ctx.threshold_push_dev(self.op, updates)
 
 
+def _check_peek_mfp(mfp):
+    """The closure shapes a full-scan peek takes (checked in the C layer
+    too): an MFP over the stored (key, val) — there is no stream side —
+    whose fields fill its out schema exactly."""
+    stream = abi.MZ_SRC_VAL_STREAM
+    reads = [f.src for f in mfp.filters[:mfp.n_filters]]
+    reads += [s for f in mfp.filters[:mfp.n_filters]
+              if f.src == abi.MZ_SRC_COMPUTE
+              for s in (f.arg0_src, f.arg1_src)]
+    for fields, want, what in (
+            (mfp.key_fields[:mfp.n_key_fields], 8 * mfp.out.key_words,
+             "key"),
+            (mfp.val_fields[:mfp.n_val_fields], mfp.out.val_bytes, "val")):
+        width = 0
+        for f in fields:
+            reads.append(f.src)
+            if f.src == abi.MZ_SRC_COMPUTE:
+                if f.off != abi.MZ_COMPUTE_CONST0:
+                    reads += [f.arg0_src, f.arg1_src]
+                width += 8  # computed fields are i64
+            else:
+                width += f.width
+        if width != want:
+            raise ValueError(
+                f"PeekPlan: mfp {what} fields are {width} bytes wide, its "
+                f"out schema says {want}")
+    if stream in reads:
+        raise ValueError("PeekPlan: mfp reads MZ_SRC_VAL_STREAM; a scan "
+                         "peek has no stream side")
+
+
+@dataclass
+class PeekPlan:
+    """A full-scan peek of an index (compute_state.rs IndexPeek without
+    literal constraints): `schema` is the arrangement's, `mfp` the peek's
+    map_filter_project as a closure over (MZ_SRC_KEY, MZ_SRC_VAL_LOOKUP),
+    None for the rows as stored. ORDER BY / LIMIT finishing
+    (RowSetFinishing) stays with the caller."""
+    schema: abi.Schema
+    mfp: Optional[abi.Closure] = None
+    allow_negative: bool = False
+
+    def __post_init__(self):
+        if self.schema.val_bytes == abi.MZ_GPU_VARLEN:
+            raise ValueError("PeekPlan: varlen arrangements unsupported")
+        if self.mfp is not None:
+            _check_peek_mfp(self.mfp)
+
+
+class PeekOp:
+    """handle_peek over a whole index: read(as_of) is the arrangement's
+    content as of that time, consolidated, in canonical order."""
+
+    def __init__(self, ctx, arr, plan: PeekPlan):
+        if not getattr(ctx, "supports_scan_peek", False):
+            raise NotImplementedError(
+                "this context does not implement the full-scan peek "
+                "(scan peek)")
+        self.ctx = ctx
+        self.arr = arr
+        self.plan = plan
+
+    def read(self, as_of) -> DevOut:
+        return self.ctx.peek_scan_dev(self.arr, as_of, self.plan.mfp,
+                                      self.plan.allow_negative)
+
+
+def render_peek(ctx, arr, plan: PeekPlan) -> PeekOp:
+    return PeekOp(ctx, arr, plan)
+
+
 def render_delta_join(ctx, arrangements, plan, exchange=None) -> DeltaJoinOp:
     return DeltaJoinOp(ctx, arrangements, plan, exchange=exchange)
 

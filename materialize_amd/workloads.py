@@ -16,8 +16,8 @@ lt otherwise (delta_join.rs:356-399).
 import numpy as np
 
 from . import _abi as abi
-from .render import (DeltaJoinPlan, DeltaPathPlan, DeltaStagePlan, ReducePlan,
-                     render_delta_join, render_reduce)
+from .render import (DeltaJoinPlan, DeltaPathPlan, DeltaStagePlan, PeekPlan,
+                     ReducePlan, render_delta_join, render_peek, render_reduce)
 from .tpch import CUTOFF_19950315 as CUTOFF
 
 F = abi.field
@@ -106,7 +106,13 @@ class Q3Dataflow:
     """TPC-H Q3 maintained incrementally: 3-path delta join + accumulable
     SUM reduce, all arrangements engine-resident. Works over any engine
     context exposing the GpuCtx interface (the oracle wrapper does too,
-    which is what the parity tests and the CPU-baseline bench leg use)."""
+    which is what the parity tests and the CPU-baseline bench leg use).
+
+    `index_output=True` (load/step only) also arranges the reduce's
+    corrections as the view's output index `arr_out`, never compacted, and
+    peek_result(t) reads the whole view back from it as of t — `CREATE
+    INDEX` on the view plus `SELECT *` from it. Needs a context with the
+    full-scan peek."""
 
     SCHEMAS = {
         "customer": (1, 8),
@@ -115,14 +121,35 @@ class Q3Dataflow:
         "lineitem": (1, 24),
     }
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, index_output=False):
         self.ctx = ctx
         self.arrs = {name: ctx.arr_create(abi.schema(kw, vb))
                      for name, (kw, vb) in self.SCHEMAS.items()}
         self.plan = q3_plan()
         self.join = render_delta_join(ctx, self.arrs, self.plan)
-        self.reduce = render_reduce(ctx, q3_reduce_plan())
+        rplan = q3_reduce_plan()
+        self.reduce = render_reduce(ctx, rplan)
         self.paths = {p.source_relation: p for p in self.plan.paths}
+        self.arr_out = self.out_peek = None
+        if index_output:
+            # not in self.arrs: the view is read at earlier times too, so
+            # _advance_compaction must leave it alone
+            self.arr_out = ctx.arr_create(rplan.spec.out)
+            self.out_peek = render_peek(ctx, self.arr_out,
+                                        PeekPlan(rplan.spec.out))
+
+    def _index_corr(self, corr, t):
+        if self.arr_out is not None and corr.n:
+            self.ctx.arr_insert(self.arr_out, corr.updates(t, t + 1))
+
+    def peek_result(self, t):
+        """The view's rows as of t (host columns), from the output index."""
+        if self.out_peek is None:
+            raise ValueError("Q3Dataflow was built without index_output")
+        out = self.out_peek.read(t)
+        cols = out.to_host()
+        out.release()
+        return cols
 
     def _seal_push(self, name, keys, vals, diffs, t):
         ctx = self.ctx
@@ -152,6 +179,7 @@ class Q3Dataflow:
         if out is not None:
             corr = self.reduce.push(out.updates(0, 1))
             n_corr = corr.n
+            self._index_corr(corr, 0)
             corr.release()
             out.release()
         return n_corr
@@ -218,6 +246,7 @@ class Q3Dataflow:
             diffs = np.concatenate([c[3] for c in cols])
             u = abi.make_updates(keys, vals, times, diffs, t, t + 1)
             corr = self.reduce.push(u)
+        self._index_corr(corr, t)
         for out in outs:
             out.release()
         return rows, corr
