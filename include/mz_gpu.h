@@ -545,6 +545,83 @@ int  mz_gpu_peek_scan(mz_gpu_ctx *ctx, mz_gpu_arr *arr, uint64_t as_of,
                       const mz_gpu_closure *mfp, int allow_negative,
                       mz_gpu_out **out);
 
+/* ------------------------------------------------------- temporal filter
+ * Replaces the temporal half of MapFilterProject — MfpPlan { lower_bounds,
+ * upper_bounds } and MfpPlan::evaluate (src/expr/src/linear.rs, mod plan;
+ * lowered from `mz_now() <cmp> expr` predicates by MfpPlan::create_from in
+ * the same file), as used by render/flat_map.rs, the join closures and
+ * persist_source. A predicate on mz_now() gives a row a
+ * validity interval, which is how sliding and tumbling windows and TTLs are
+ * written (WHERE mz_now() >= ts AND mz_now() < ts + 30000).
+ *
+ * Row semantics, for an input update (key, val, t, d):
+ *  1. The mfp's filters run first; a failing row yields nothing.
+ *  2. lo = t, hi = none; the bounds are evaluated in spec order. A NULL
+ *     datum: the row yields nothing (the predicate is NULL). v = datum + add
+ *     is computed exactly, in 128 bits; v < 0 is not an mz_timestamp and
+ *     yields the one error row (MZ_ERR_TIMESTAMP_OUT_OF_RANGE, t, d) and no
+ *     ok row. MZ_TB_LOWER: lo = max(lo, v). MZ_TB_UPPER: hi = min(hi, v).
+ *  3. hi exists and hi <= lo: the row yields nothing.
+ *  4. Otherwise (proj(row), lo, d) unless lo >= until, and, if hi exists and
+ *     hi < until, (proj(row), hi, -d); the negation wraps, as Diff does.
+ * Unlike the reference, the projection may not contain a field that can
+ * error (MZ_COMPUTE_DIV_I64): put it in a following map
+ * call. Bound errors are emitted at the input time and are never held.
+ *
+ * Frontier and hold-back. The -d update usually lies in the future, beyond
+ * the batch's upper. Timely lets such updates travel and the downstream
+ * arrange batcher holds them; here the operator owns them. It keeps a
+ * frontier f: UINT64_MAX (in stats) before the first push, which sets it to
+ * delta.lower. A push must have delta.lower == f, upper >= lower and every
+ * input time in [lower, upper); anything else is an error that leaves the
+ * state untouched. Its out-batch is every update with time < delta.upper,
+ * from this delta and from the held buffer, consolidated and in canonical
+ * order; bound errors arrive in its error stream. Everything else stays
+ * held, itself consolidated, so an insert's -d at hi cancels against the +d
+ * at hi of the row's later deletion. f becomes delta.upper. An empty delta
+ * with an advanced upper is a legal frontier tick that releases
+ * expirations. All output times lie in [lower, upper): safe to insert into
+ * an arrangement or push into a multi-timestamp reduce with those bounds.
+ *
+ * Refused at create (NULL, message in last_error): a varlen schema; an mfp
+ * that reads MZ_SRC_VAL_LOOKUP, reads past the input row, has a
+ * MZ_COMPUTE_DIV_I64 field, or whose out schema is wider than 2 key words /
+ * 64 val bytes; n_bounds == 0 or > MZ_GPU_MAX_BOUNDS; a bound of unknown
+ * kind, of a source other than the input row, of width other than 4 or 8,
+ * or reading past the row. */
+enum { MZ_TB_LOWER = 0,   /* mz_now() >= v : v is a lower bound (inclusive)  */
+       MZ_TB_UPPER = 1 }; /* mz_now() <  v : v is an upper bound (exclusive) */
+typedef struct {
+  uint8_t  kind;      /* MZ_TB_*                                            */
+  uint8_t  src;       /* MZ_SRC_KEY or MZ_SRC_VAL_STREAM (the input row)    */
+  uint16_t off;       /* byte offset of the datum                           */
+  uint8_t  width;     /* 4 or 8, signed LE, sign-extended                   */
+  uint8_t  nullable;  /* null indicator byte at off+width, as aggregates    */
+  int64_t  add;       /* v = datum + add, computed exactly (no wrap)        */
+} mz_gpu_time_bound;
+#define MZ_GPU_MAX_BOUNDS 4
+typedef struct {
+  mz_gpu_schema in;
+  int32_t  has_mfp;  mz_gpu_closure mfp;   /* filters + projection over
+                        (MZ_SRC_KEY, MZ_SRC_VAL_STREAM); 0 = identity       */
+  uint32_t n_bounds; mz_gpu_time_bound bounds[MZ_GPU_MAX_BOUNDS]; /* >= 1   */
+  uint64_t until;          /* outputs at time >= until are dropped;
+                              UINT64_MAX = none                             */
+  uint64_t initial_rows;   /* held-buffer capacity hint; 0 = default        */
+} mz_gpu_temporal_spec;
+typedef struct mz_gpu_temporal mz_gpu_temporal;
+mz_gpu_temporal *mz_gpu_temporal_create(mz_gpu_ctx *ctx,
+                                        const mz_gpu_temporal_spec *spec);
+int  mz_gpu_temporal_push(mz_gpu_ctx *ctx, mz_gpu_temporal *op,
+                          const mz_gpu_updates *delta, mz_gpu_out **out);
+/* Held row count, the smallest held time (UINT64_MAX when nothing is held:
+ * the first tick that produces output is the one past it) and f. */
+int  mz_gpu_temporal_stats(mz_gpu_ctx *ctx, mz_gpu_temporal *op,
+                           uint64_t *held_rows, uint64_t *next_time,
+                           uint64_t *frontier);
+void mz_gpu_temporal_drop(mz_gpu_ctx *ctx, mz_gpu_temporal *op);
+enum { MZ_ERR_TIMESTAMP_OUT_OF_RANGE = 2 };
+
 /* The routing hash itself (host helper; device code uses the same). */
 uint64_t mz_gpu_route_hash(const uint64_t *key_words, uint32_t n_words);
 

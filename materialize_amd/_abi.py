@@ -151,6 +151,39 @@ class TopKSpec(C.Structure):
 
 
 MZ_ERR_DIVISION_BY_ZERO = 1
+MZ_ERR_TIMESTAMP_OUT_OF_RANGE = 2
+
+# temporal filter (mz_gpu_temporal_*): mz_now() bounds
+MZ_TB_LOWER, MZ_TB_UPPER = 0, 1
+MZ_GPU_MAX_BOUNDS = 4
+MAX_KW, MAX_VB = 2, 64  # widest fixed-width row an operator's kernels hold
+
+
+class TimeBound(C.Structure):
+    """mz_gpu_time_bound: mz_now() >= v (LOWER) or mz_now() < v (UPPER),
+    v = the row's datum + add."""
+    _fields_ = [
+        ("kind", C.c_uint8),
+        ("src", C.c_uint8),
+        ("off", C.c_uint16),
+        ("width", C.c_uint8),
+        ("nullable", C.c_uint8),
+        ("add", C.c_int64),
+    ]
+
+
+class TemporalSpec(C.Structure):
+    """mz_gpu_temporal_spec: an MFP with temporal predicates over one input
+    stream."""
+    _fields_ = [
+        ("in_", Schema),
+        ("has_mfp", C.c_int32),
+        ("mfp", Closure),
+        ("n_bounds", C.c_uint32),
+        ("bounds", TimeBound * MZ_GPU_MAX_BOUNDS),
+        ("until", C.c_uint64),
+        ("initial_rows", C.c_uint64),
+    ]
 
 
 class OutBatch(C.Structure):
@@ -394,3 +427,128 @@ def collation_parts(spec):
     parts = [acc] if acc else []
     parts += [[i] for i in idx if is_hierarchical(spec.aggs[i])]
     return parts
+
+
+def time_bound(cmp, src, off, width=8, add=0, nullable=0):
+    """The bounds of the SQL predicate `mz_now() <cmp> datum + add`, as a
+    list — the lowering of MfpPlan::create_from (src/expr/src/linear.rs),
+    which steps `<=` and `>` forward by one to reach the two canonical
+    forms `mz_now() >= v` (LOWER) and `mz_now() < v` (UPPER). `=` is both;
+    `<>` is not a temporal predicate (ValueError, as the reference rejects
+    it)."""
+    def b(kind, a):
+        if not -2**63 <= a < 2**63:
+            raise ValueError(f"temporal: bound offset {a} is not an i64")
+        return TimeBound(kind=kind, src=src, off=off, width=width,
+                         nullable=1 if nullable else 0, add=a)
+    if cmp == MZ_CMP_GE:
+        return [b(MZ_TB_LOWER, add)]
+    if cmp == MZ_CMP_GT:
+        return [b(MZ_TB_LOWER, add + 1)]
+    if cmp == MZ_CMP_LT:
+        return [b(MZ_TB_UPPER, add)]
+    if cmp == MZ_CMP_LE:
+        return [b(MZ_TB_UPPER, add + 1)]
+    if cmp == MZ_CMP_EQ:
+        return [b(MZ_TB_LOWER, add), b(MZ_TB_UPPER, add + 1)]
+    raise ValueError("temporal: mz_now() <> expr is not a temporal "
+                     f"predicate (comparator {cmp})")
+
+
+def _closure_reads(cl):
+    """(src, off, bytes) of every read a closure makes of its inputs, and
+    its fields as (field, is_val) pairs."""
+    reads = []
+    for f in cl.filters[:cl.n_filters]:
+        w = 4 if f.width == 4 else 8
+        if f.src != MZ_SRC_COMPUTE:
+            reads.append((f.src, f.off, w))
+        elif f.off == MZ_COMPUTE_Q17_QTYLT:
+            reads += [(f.arg0_src, f.arg0, 8), (f.arg1_src, f.arg1, 32)]
+        elif f.off == MZ_COMPUTE_CMP_FIELDS:
+            reads += [(f.arg0_src, f.arg0, w), (f.arg1_src, f.arg1, w)]
+    for f in (list(cl.key_fields[:cl.n_key_fields])
+              + list(cl.val_fields[:cl.n_val_fields])):
+        if f.src != MZ_SRC_COMPUTE:
+            reads.append((f.src, f.off, f.width))
+        elif f.off != MZ_COMPUTE_CONST0:
+            reads += [(f.arg0_src, f.arg0, 8), (f.arg1_src, f.arg1, 8)]
+    return reads
+
+
+def temporal_spec(in_schema, bounds, mfp=None, until=None, initial_rows=0):
+    """mz_gpu_temporal_spec for the temporal predicates `bounds` (TimeBound
+    items or the lists time_bound returns, in evaluation order) over rows of
+    `in_schema`, with the non-temporal filters and the projection in `mfp`
+    (a closure over MZ_SRC_KEY / MZ_SRC_VAL_STREAM; None = the row as it
+    is). `until` drops outputs at or beyond it (None = no limit). Checks the
+    operator's create-time restrictions here as well as in the C layer
+    (ValueError)."""
+    flat = []
+    for b in bounds:
+        flat += list(b) if isinstance(b, (list, tuple)) else [b]
+    kw, vb = in_schema.key_words, in_schema.val_bytes
+    if vb == MZ_GPU_VARLEN:
+        raise ValueError("temporal: varlen vals unsupported")
+    if not 1 <= kw <= MAX_KW or vb > MAX_VB:
+        raise ValueError("temporal: in schema must have 1..2 key words and "
+                         "at most 64 val bytes")
+    if not 1 <= len(flat) <= MZ_GPU_MAX_BOUNDS:
+        raise ValueError(f"temporal: n_bounds must be 1..{MZ_GPU_MAX_BOUNDS}"
+                         f", got {len(flat)}")
+
+    def room(src):
+        return 8 * kw if src == MZ_SRC_KEY else vb
+
+    for i, b in enumerate(flat):
+        if b.kind not in (MZ_TB_LOWER, MZ_TB_UPPER):
+            raise ValueError(f"temporal: bound {i}: unknown kind {b.kind}")
+        if b.src not in (MZ_SRC_KEY, MZ_SRC_VAL_STREAM):
+            raise ValueError(f"temporal: bound {i} must read MZ_SRC_KEY or "
+                             "MZ_SRC_VAL_STREAM")
+        if b.width not in (4, 8):
+            raise ValueError(f"temporal: bound {i}: width must be 4 or 8")
+        if b.off + b.width + (1 if b.nullable else 0) > room(b.src):
+            raise ValueError(f"temporal: bound {i} reads past the input "
+                             "row's key or val (offset out of range)")
+    if mfp is not None:
+        for src, off, nbytes in _closure_reads(mfp):
+            if src == MZ_SRC_VAL_LOOKUP:
+                raise ValueError("temporal: mfp reads MZ_SRC_VAL_LOOKUP; a "
+                                 "temporal filter has no lookup side")
+            if src not in (MZ_SRC_KEY, MZ_SRC_VAL_STREAM):
+                raise ValueError(f"temporal: mfp reads unknown source {src}")
+            if off + nbytes > room(src):
+                raise ValueError("temporal: mfp reads past the input row's "
+                                 "key or val (offset out of range)")
+        for fields, want, what in (
+                (mfp.key_fields[:mfp.n_key_fields], 8 * mfp.out.key_words,
+                 "key"),
+                (mfp.val_fields[:mfp.n_val_fields], mfp.out.val_bytes,
+                 "val")):
+            width = 0
+            for f in fields:
+                if f.src == MZ_SRC_COMPUTE and f.off == MZ_COMPUTE_DIV_I64:
+                    raise ValueError(
+                        "temporal: the projection may not contain a field "
+                        "that can error (MZ_COMPUTE_DIV_I64); put the "
+                        "division in a following map")
+                width += 8 if f.src == MZ_SRC_COMPUTE else f.width
+            if width != want:
+                raise ValueError(f"temporal: mfp {what} fields are {width} "
+                                 f"bytes wide, its out schema says {want}")
+        if not 1 <= mfp.out.key_words <= MAX_KW \
+                or mfp.out.val_bytes > MAX_VB:
+            raise ValueError("temporal: mfp out schema wider than 2 key "
+                             "words / 64 val bytes")
+    sp = TemporalSpec()
+    sp.in_ = in_schema
+    sp.has_mfp = 0 if mfp is None else 1
+    if mfp is not None:
+        sp.mfp = mfp
+    sp.n_bounds = len(flat)
+    for i, b in enumerate(flat):
+        sp.bounds[i] = b
+    sp.until = 0xFFFFFFFFFFFFFFFF if until is None else until
+    sp.initial_rows = initial_rows
+    return sp

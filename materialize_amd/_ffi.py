@@ -9,7 +9,7 @@ import os
 import subprocess
 
 from ._abi import (Closure, CollationSpec, OutBatch, ReduceSpec, Schema,
-                   TopKSpec, Updates, out_to_numpy)
+                   TemporalSpec, TopKSpec, Updates, out_to_numpy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "csrc", "libmzgpu.so")
@@ -147,6 +147,15 @@ def load():
     lib.mz_gpu_peek_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.POINTER(Closure), C.c_int,
                                      C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_temporal_create.restype = C.c_void_p
+    lib.mz_gpu_temporal_create.argtypes = [C.c_void_p,
+                                           C.POINTER(TemporalSpec)]
+    lib.mz_gpu_temporal_push.argtypes = [C.c_void_p, C.c_void_p,
+                                         C.POINTER(Updates),
+                                         C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_temporal_stats.argtypes = [C.c_void_p, C.c_void_p] + \
+        [C.POINTER(C.c_uint64)] * 3
+    lib.mz_gpu_temporal_drop.argtypes = [C.c_void_p, C.c_void_p]
     lib.mz_gpu_route_hash.restype = C.c_uint64
     lib.mz_gpu_route_hash.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
     lib.mz_gpu_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -167,6 +176,9 @@ class GpuCtx:
     # Full-scan peeks (mz_gpu_peek_scan) are implemented here; render_peek
     # refuses contexts that do not say so.
     supports_scan_peek = True
+    # Temporal filters (mz_gpu_temporal_*) are implemented here;
+    # render_temporal_filter refuses contexts that do not say so.
+    supports_temporal_filter = True
 
     def __init__(self, device=0):
         self.lib = load()
@@ -416,6 +428,37 @@ class GpuCtx:
         raises MzGpuError unless `allow_negative`."""
         return self._take(self._peek_scan(arr, as_of, mfp, allow_negative))
 
+    def temporal_create(self, spec):
+        op = self.lib.mz_gpu_temporal_create(self.ctx, C.byref(spec))
+        if not op:
+            raise MzGpuError(self.lib.mz_gpu_last_error(self.ctx).decode())
+        return op
+
+    def _temporal_push(self, op, upd):
+        outp = C.POINTER(OutBatch)()
+        self._check(self.lib.mz_gpu_temporal_push(self.ctx, op,
+                                                  C.byref(upd),
+                                                  C.byref(outp)))
+        return outp
+
+    def temporal_push(self, op, upd):
+        """Push a delta with bounds [lower, upper) through a temporal
+        filter: host columns of every update below `upper`, from this delta
+        and from the held buffer, consolidated; bound errors land in
+        self.last_errs. An empty delta is a frontier tick."""
+        return self._take(self._temporal_push(op, upd))
+
+    def temporal_stats(self, op):
+        """(held rows, smallest held time, frontier); the times are
+        2**64 - 1 when nothing is held / before the first push."""
+        held, nxt, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mz_gpu_temporal_stats(
+            self.ctx, op, C.byref(held), C.byref(nxt), C.byref(f)))
+        return held.value, nxt.value, f.value
+
+    def temporal_drop(self, op):
+        self.lib.mz_gpu_temporal_drop(self.ctx, op)
+
     # --- device-resident variants (outputs stay on the GPU; used by the
     # render layer to chain stages without host round trips) ---
     def _dev_out(self, outp, sorted=False):
@@ -451,6 +494,10 @@ class GpuCtx:
         # consolidated output in canonical order
         return self._dev_out(
             self._peek_scan(arr, as_of, mfp, allow_negative), sorted=True)
+
+    def temporal_push_dev(self, op, upd):
+        # consolidated output in canonical order
+        return self._dev_out(self._temporal_push(op, upd), sorted=True)
 
     def halfjoin_dev(self, lookup, upd, stream_vb, le, cl):
         # raw (unconsolidated) output: the render layer's consumers —

@@ -844,6 +844,198 @@ __global__ void k_any_negative(const i64 *diffs, u64 n,
   }
 }
 
+// ------------------------------------------------------ temporal filter
+// MfpPlan::evaluate (src/expr/src/linear.rs) restated: the mz_now() bounds
+// of a temporal MapFilterProject give each input update a validity
+// interval [lo, hi) and turn it into up to two output updates, +d at lo and
+// -d at hi. The bounds travel by value.
+struct TemporalBounds {
+  u32 n;
+  mz_gpu_time_bound b[MZ_GPU_MAX_BOUNDS];
+  u64 until;
+};
+
+// The operator's third queue next to an EmitQueue: the updates at or beyond
+// the push's upper, which stay held. Its row counter is q.ctr[2]; q.ctr[3]
+// counts input times outside [lower, upper).
+struct HeldQueue {
+  u64 cap;
+  u64 *keys;
+  u8 *vals;
+  u64 *times;
+  i64 *diffs;
+};
+
+// One row's window, bounds evaluated in spec order (mz_gpu.h, row semantics
+// 2-3). Returns 0 = the row yields nothing (a NULL bound or an empty
+// window), 1 = [*lo, *hi) with *has_hi telling whether an upper bound
+// exists, 2 = a bound is not an mz_timestamp (the error row).
+__device__ __forceinline__ int d_temporal_window(const TemporalBounds &tb,
+                                                 const u64 *key,
+                                                 const u8 *val, u64 t,
+                                                 u64 *lo, u64 *hi,
+                                                 bool *has_hi) {
+  u64 l = t, h = 0;
+  bool hh = false;
+  for (u32 i = 0; i < tb.n; i++) {
+    const mz_gpu_time_bound b = tb.b[i];
+    const u8 *p = (b.src == MZ_SRC_KEY ? (const u8 *)key : val) + b.off;
+    if (b.nullable && p[b.width] != 0) return 0;
+    // datum + add in 128 bits: [-2^64, 2^64 - 2], never wrapped
+    i128 v = (i128)d_read_int(p, b.width) + (i128)b.add;
+    if (v < 0) return 2;
+    u64 u = (u64)v;
+    if (b.kind == MZ_TB_LOWER) {
+      if (u > l) l = u;
+    } else if (!hh || u < h) {
+      h = u;
+      hh = true;
+    }
+  }
+  *lo = l;
+  *hi = h;
+  *has_hi = hh;
+  return (hh && h <= l) ? 0 : 1;
+}
+
+// Slot `idx` of the ready queue (when the update's time is below the push's
+// upper) or of the held queue: writes time and diff and hands back where
+// the row's key and val go.
+struct RowSlot {
+  u64 *k;
+  u8 *v;
+};
+__device__ __forceinline__ RowSlot d_temporal_slot(bool ready,
+                                                   const EmitQueue &q,
+                                                   const HeldQueue &h,
+                                                   u32 okw, u32 ovb, u64 idx,
+                                                   u64 time, i64 diff) {
+  if (ready) {
+    q.otimes[idx] = time;
+    q.odiffs[idx] = diff;
+    return {q.okeys + idx * okw, q.ovals + idx * ovb};
+  }
+  h.times[idx] = time;
+  h.diffs[idx] = diff;
+  return {h.keys + idx * okw, h.vals + idx * ovb};
+}
+
+// One work item per input update (grid-stride). A lane counts what its row
+// emits — c_ready and c_held in {0,1,2} ok rows, e in {0,1} error rows —
+// and the wave reserves its slices of the three queues; the fields go
+// straight to the reserved slots. The queues are sized at their exact
+// bounds (2n ready, 2n held beyond what the held queue already has, n
+// errors), so nothing overflows and nothing is relaunched. Every lane of a
+// wave runs the same number of iterations and reaches both reservations in
+// each one (the row index is clamped; idle lanes reserve nothing).
+// The closure's filters run in count mode first; its projection runs once
+// per emitting row, into the row's first slot, and a two-update row's second
+// slot is a copy of the first.
+__global__ void k_temporal_eval(DeltaView d, u64 lower, u64 upper,
+                                const mz_gpu_closure cl,
+                                const TemporalBounds tb, EmitQueue q,
+                                HeldQueue h) {
+  u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  u64 stride = (u64)gridDim.x * blockDim.x;
+  u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  u64 iters = (d.n + stride - 1) / stride;  // uniform across the wave
+  u32 lane = threadIdx.x & 63;
+  for (u64 it = 0; it < iters; it++) {
+    u64 idx = start + it * stride;
+    bool valid = idx < d.n;
+    const DeltaView::Row r = d.row(valid ? idx : d.n - 1);
+    u64 lo = 0, hi = 0;
+    bool e_lo = false, e_hi = false;  // the +d and the -d update
+    u32 e = 0;
+    if (valid) {
+      if (r.t < lower || r.t >= upper) {
+        atomicAdd(q.ctr + 3, 1ull);  // the host refuses the push
+      } else if (d_closure_apply(&cl, r.key, r.val, nullptr, nullptr,
+                                 nullptr)) {
+        bool has_hi;
+        int w = d_temporal_window(tb, r.key, r.val, r.t, &lo, &hi, &has_hi);
+        if (w == 2) {
+          e = 1;
+        } else if (w == 1) {
+          e_lo = lo < tb.until;
+          e_hi = has_hi && hi < tb.until;
+        }
+      }
+    }
+    bool r_lo = e_lo && lo < upper, r_hi = e_hi && hi < upper;
+    u32 c_ready = (u32)r_lo + (u32)r_hi;
+    u32 c_held = (u32)(e_lo && !r_lo) + (u32)(e_hi && !r_hi);
+    u64 o, eo;
+    (void)q.reserve(c_ready, e, lane, &o, &eo);
+    u64 ho = wave_reserve(q.ctr + 2, c_held, lane);
+    // the capacities are exact bounds; a slice past one is never written
+    if (!(c_ready | c_held | e) || o + c_ready > q.cap || eo + e > q.ecap ||
+        ho + c_held > h.cap)
+      continue;
+    if (e) {  // emitted at the input time, never held
+      q.ecodes[eo] = MZ_ERR_TIMESTAMP_OUT_OF_RANGE;
+      q.etimes[eo] = r.t;
+      q.ediffs[eo] = r.d;
+      continue;
+    }
+    RowSlot s0{nullptr, nullptr}, s1{nullptr, nullptr};
+    if (e_lo) {
+      s0 = d_temporal_slot(r_lo, q, h, okw, ovb, r_lo ? o : ho, lo, r.d);
+      (r_lo ? o : ho)++;
+    }
+    if (e_hi) {  // the negation wraps, as Diff does
+      RowSlot s = d_temporal_slot(r_hi, q, h, okw, ovb, r_hi ? o : ho, hi,
+                                  (i64)(0 - (u64)r.d));
+      (e_lo ? s1 : s0) = s;
+    }
+    (void)d_closure_apply(&cl, r.key, r.val, nullptr, s0.k, s0.v);
+    if (s1.k) {
+      for (u32 w = 0; w < okw; w++) s1.k[w] = s0.k[w];
+      for (u32 c = 0; c < ovb; c++) s1.v[c] = s0.v[c];
+    }
+  }
+}
+
+// One pass over the resident held columns (kw/vb = the operator's output
+// schema): a row whose time is below `upper` is appended to the ready
+// queue, every other row to the held queue — the same wave-aggregated
+// reservations as k_temporal_eval, on the same counters.
+__global__ void k_temporal_release(const u64 *keys, const u8 *vals,
+                                   const u64 *times, const i64 *diffs, u64 n,
+                                   u32 kw, u32 vb, u64 upper, EmitQueue q,
+                                   HeldQueue h) {
+  u64 stride = (u64)gridDim.x * blockDim.x;
+  u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  u64 iters = (n + stride - 1) / stride;  // uniform across the wave
+  u32 lane = threadIdx.x & 63;
+  for (u64 it = 0; it < iters; it++) {
+    u64 idx = start + it * stride;
+    bool valid = idx < n;
+    u64 i = valid ? idx : n - 1;
+    u64 t = times[i];
+    bool rdy = valid && t < upper, stay = valid && !rdy;
+    u64 o = wave_reserve(q.ctr, rdy ? 1u : 0u, lane);
+    u64 ho = wave_reserve(q.ctr + 2, stay ? 1u : 0u, lane);
+    if (!valid || (rdy ? o >= q.cap : ho >= h.cap)) continue;
+    RowSlot s = d_temporal_slot(rdy, q, h, kw, vb, rdy ? o : ho, t, diffs[i]);
+    for (u32 w = 0; w < kw; w++) s.k[w] = keys[i * kw + w];
+    for (u32 c = 0; c < vb; c++) s.v[c] = vals[i * vb + c];
+  }
+}
+
+// Smallest of the first *np times into *out (which starts at ~0): the
+// held buffer's next release time, read back with the push's closing copy.
+__global__ void k_time_min(const u64 *times, const u64 *np,
+                           unsigned long long *out) {
+  u64 n = *np, m = ~0ull;
+  GRID_STRIDE(i, n) m = times[i] < m ? times[i] : m;
+  for (int s = 32; s; s >>= 1) {
+    u64 other = (u64)__shfl_xor((int64_t)m, s, 64);
+    m = other < m ? other : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m != ~0ull) atomicMin(out, m);
+}
+
 // Fused two-stage delta-path probe (one delta path's two lookup stages,
 // delta_join.rs:338-472, in a single kernel): a stage-1 match produces
 // its intermediate (key2, val2) in REGISTERS and immediately probes the
@@ -2309,6 +2501,7 @@ struct Ctx {
   std::vector<mz_gpu_join *> joins;
   std::vector<mz_gpu_red *> reds;
   std::vector<struct mz_gpu_collation *> cols;
+  std::vector<struct mz_gpu_temporal *> temporals;
   // pinned staging for small device->host readbacks (pageable-staged
   // async copies cost tens of microseconds each; the step does ~a dozen)
   void *pin = nullptr;
@@ -4277,6 +4470,8 @@ static void arr_flush_impl(Ctx *ctx, mz_gpu_arr *a);
 // frees a collation's stitch state and minmax parts (its accumulable
 // sub-reduce lives in ctx->reds); defined with the operator
 static void collation_free(mz_gpu_ctx *c, mz_gpu_collation *op);
+// frees a temporal filter's held buffer; defined with the operator
+static void temporal_free(Ctx *ctx, struct mz_gpu_temporal *op);
 
 // The reduce operator's device state: accumulator table, counters and the
 // distinct aggregates' pair tables.
@@ -4440,6 +4635,8 @@ void mz_gpu_fini(mz_gpu_ctx *c) {
   ctx->reds.clear();
   for (mz_gpu_collation *co : ctx->cols) collation_free(c, co);
   ctx->cols.clear();
+  for (mz_gpu_temporal *tf : ctx->temporals) temporal_free(ctx, tf);
+  ctx->temporals.clear();
   for (mz_gpu_join *j : ctx->joins) delete j;
   ctx->joins.clear();
   (void)hipStreamSynchronize(ctx->stream);
@@ -5122,35 +5319,39 @@ int mz_gpu_peek(mz_gpu_ctx *c, mz_gpu_arr *arr, const uint64_t *keys,
   return probe_impl(&c->impl, arr, &u, 0, PM_HALF_LE, 0, &cl, 1, out);
 }
 
-// The closure shapes a full-scan peek accepts: an MFP over (key, val) —
-// the arrangement's val is the lookup side and no stream side exists.
-// Every read must stay inside the kw key words / vb val bytes.
-static const char *peek_scan_mfp_error(const mz_gpu_closure *cl, u32 kw,
-                                       u32 vb) {
+// The closure shapes an MFP over one (key, val) row may take: the val is
+// one of the closure's two val sides and the other, `absent`, does not
+// exist (a full-scan peek has no stream side, a temporal filter no lookup
+// side). Every read must stay inside the kw key words / vb val bytes.
+// Returns the message, prefixed with `who`, or "" when the shape is fine.
+static std::string mfp_shape_error(const char *who, const mz_gpu_closure *cl,
+                                   u32 kw, u32 vb, u8 absent,
+                                   const char *absent_why,
+                                   const char *row_name) {
+  const std::string w = std::string(who) + ": mfp ";
   if (cl->n_filters > MZ_GPU_MAX_FILTERS ||
       cl->n_key_fields > MZ_GPU_MAX_FIELDS ||
       cl->n_val_fields > MZ_GPU_MAX_FIELDS)
-    return "peek_scan: mfp filter/field count out of range";
+    return w + "filter/field count out of range";
   if (cl->out.key_words == 0 || cl->out.key_words > (u32)MAX_KW ||
       cl->out.val_bytes > (u32)MAX_VB)
-    return "peek_scan: mfp out schema unsupported (1..2 key words, "
-           "fixed-width val of at most 64 bytes)";
-  const char *stream = "peek_scan: mfp reads MZ_SRC_VAL_STREAM (a scan has "
-                       "no stream side)";
-  const char *past = "peek_scan: mfp reads past the arrangement's key or val";
+    return w + "out schema unsupported (1..2 key words, "
+               "fixed-width val of at most 64 bytes)";
+  const std::string stream = w + "reads " + absent_why;
+  const std::string past = w + "reads past " + row_name;
   // as d_cl_src resolves a source: the key, else the stored val
   auto fits = [&](u8 src, u32 off, u32 bytes) {
     return (u64)off + bytes <= (src == MZ_SRC_KEY ? 8ull * kw : (u64)vb);
   };
   for (u32 i = 0; i < cl->n_filters; i++) {
     const mz_gpu_filter &f = cl->filters[i];
-    if (f.src == MZ_SRC_VAL_STREAM) return stream;
+    if (f.src == absent) return stream;
     u32 w = f.width == 4 ? 4 : 8;  // d_read_int
     if (f.src != MZ_SRC_COMPUTE) {
       if (!fits(f.src, f.off, w)) return past;
       continue;
     }
-    if (f.arg0_src == MZ_SRC_VAL_STREAM || f.arg1_src == MZ_SRC_VAL_STREAM)
+    if (f.arg0_src == absent || f.arg1_src == absent)
       return stream;
     if (f.off == MZ_COMPUTE_Q17_QTYLT &&  // i64; i128 sum + count at +24
         !(fits(f.arg0_src, f.arg0, 8) && fits(f.arg1_src, f.arg1, 32)))
@@ -5165,10 +5366,10 @@ static const char *peek_scan_mfp_error(const mz_gpu_closure *cl, u32 kw,
     u64 bytes = 0;
     for (u32 i = 0; i < nf; i++) {
       const mz_gpu_field &f = fs[i];
-      if (f.src == MZ_SRC_VAL_STREAM) return stream;
+      if (f.src == absent) return stream;
       if (f.src == MZ_SRC_COMPUTE && f.off != MZ_COMPUTE_CONST0) {
-        if (f.arg0_src == MZ_SRC_VAL_STREAM ||
-            f.arg1_src == MZ_SRC_VAL_STREAM)
+        if (f.arg0_src == absent ||
+            f.arg1_src == absent)
           return stream;
         if (!(fits(f.arg0_src, f.arg0, 8) && fits(f.arg1_src, f.arg1, 8)))
           return past;
@@ -5178,9 +5379,9 @@ static const char *peek_scan_mfp_error(const mz_gpu_closure *cl, u32 kw,
       bytes += f.src == MZ_SRC_COMPUTE ? 8 : f.width;  // computes are i64
     }
     if (bytes != (which ? (u64)cl->out.val_bytes : 8ull * cl->out.key_words))
-      return "peek_scan: mfp field widths do not add up to its out schema";
+      return w + "field widths do not add up to its out schema";
   }
-  return nullptr;
+  return std::string();
 }
 
 // Full-scan peek host path: the probe protocol with
@@ -5196,7 +5397,11 @@ static int peek_scan_impl(Ctx *ctx, mz_gpu_arr *arr, u64 as_of,
   u32 kw = arr->schema.kw, vb = arr->schema.vb;
   mz_gpu_closure cl{};
   if (mfp) {
-    if (const char *why = peek_scan_mfp_error(mfp, kw, vb)) {
+    std::string why = mfp_shape_error(
+        "peek_scan", mfp, kw, vb, MZ_SRC_VAL_STREAM,
+        "MZ_SRC_VAL_STREAM (a scan has no stream side)",
+        "the arrangement's key or val");
+    if (!why.empty()) {
       ctx->err = why;
       return 1;
     }
@@ -5287,6 +5492,280 @@ int mz_gpu_peek_scan(mz_gpu_ctx *c, mz_gpu_arr *arr, uint64_t as_of,
                      const mz_gpu_closure *mfp, int allow_negative,
                      mz_gpu_out **out) {
   return peek_scan_impl(&c->impl, arr, as_of, mfp, allow_negative, out);
+}
+
+// ------------------------------------------------------ temporal filter
+// The operator that owns future-stamped updates (mz_gpu.h):
+// the held buffer is operator-owned flat columns of `cap` rows, the first
+// n_held of them consolidated; min_time mirrors the smallest held time.
+struct mz_gpu_temporal {
+  mz_gpu_closure cl;  // the mfp, or the identity projection
+  TemporalBounds tb;
+  u32 kw, vb;         // input schema; the held rows have cl.out's
+  FlatCols held;
+  u64 cap = 0, n_held = 0;
+  u64 min_time = ~0ull;
+  u64 frontier = ~0ull;
+  bool started = false;
+};
+
+static void temporal_free(Ctx *ctx, mz_gpu_temporal *op) {
+  flat_free(ctx, op->held);
+  delete op;
+}
+
+mz_gpu_temporal *mz_gpu_temporal_create(mz_gpu_ctx *c,
+                                        const mz_gpu_temporal_spec *spec) {
+  Ctx *ctx = &c->impl;
+  auto fail = [&](const std::string &msg) -> mz_gpu_temporal * {
+    ctx->err = msg;
+    return nullptr;
+  };
+  u32 kw = spec->in.key_words, vb = spec->in.val_bytes;
+  if (is_varlen(vb)) return fail("temporal: varlen vals unsupported");
+  if (kw < 1 || kw > (u32)MAX_KW || vb > (u32)MAX_VB)
+    return fail("temporal: in schema unsupported (1..2 key words, "
+                "fixed-width val of at most 64 bytes)");
+  if (spec->n_bounds < 1 || spec->n_bounds > MZ_GPU_MAX_BOUNDS)
+    return fail("temporal: n_bounds must be 1.." +
+                std::to_string(MZ_GPU_MAX_BOUNDS));
+  for (u32 i = 0; i < spec->n_bounds; i++) {
+    const mz_gpu_time_bound &b = spec->bounds[i];
+    if (b.kind != MZ_TB_LOWER && b.kind != MZ_TB_UPPER)
+      return fail("temporal: bound of unknown kind");
+    if (b.src != MZ_SRC_KEY && b.src != MZ_SRC_VAL_STREAM)
+      return fail("temporal: a bound reads MZ_SRC_KEY or MZ_SRC_VAL_STREAM");
+    if (b.width != 4 && b.width != 8)
+      return fail("temporal: bound width must be 4 or 8");
+    if ((u64)b.off + b.width + (b.nullable ? 1 : 0) >
+        (b.src == MZ_SRC_KEY ? 8ull * kw : (u64)vb))
+      return fail("temporal: a bound reads past the input row's key or val");
+  }
+  mz_gpu_closure cl{};
+  if (spec->has_mfp) {
+    cl = spec->mfp;
+    std::string why = mfp_shape_error(
+        "temporal", &cl, kw, vb, MZ_SRC_VAL_LOOKUP,
+        "MZ_SRC_VAL_LOOKUP (a temporal filter has no lookup side)",
+        "the input row's key or val");
+    if (!why.empty()) return fail(why);
+    // d_cl_src sends every source but the key and the stream val to the
+    // lookup side, which does not exist here
+    auto row_src = [](u8 s) {
+      return s == MZ_SRC_KEY || s == MZ_SRC_VAL_STREAM;
+    };
+    const char *src = "temporal: mfp reads a source other than the input row";
+    for (u32 i = 0; i < cl.n_filters; i++) {
+      const mz_gpu_filter &f = cl.filters[i];
+      if (f.src == MZ_SRC_COMPUTE ? !(row_src(f.arg0_src) &&
+                                      row_src(f.arg1_src))
+                                  : !row_src(f.src))
+        return fail(src);
+    }
+    for (int which = 0; which < 2; which++) {
+      u32 nf = which ? cl.n_val_fields : cl.n_key_fields;
+      const mz_gpu_field *fs = which ? cl.val_fields : cl.key_fields;
+      for (u32 i = 0; i < nf; i++) {
+        const mz_gpu_field &f = fs[i];
+        if (f.src != MZ_SRC_COMPUTE) {
+          if (!row_src(f.src)) return fail(src);
+          continue;
+        }
+        if (f.off == MZ_COMPUTE_DIV_I64)
+          return fail("temporal: the projection may not contain a field "
+                      "that can error (MZ_COMPUTE_DIV_I64); put the "
+                      "division in a following mz_gpu_map");
+        if (f.off != MZ_COMPUTE_CONST0 &&
+            !(row_src(f.arg0_src) && row_src(f.arg1_src)))
+          return fail(src);
+      }
+    }
+  } else {  // identity: (key, val) as they arrive
+    cl.n_key_fields = 1;
+    cl.key_fields[0] = mz_gpu_field{MZ_SRC_KEY, 0, (u8)(8 * kw), 0, 0, 0, 0};
+    cl.n_val_fields = vb ? 1u : 0u;
+    if (vb)
+      cl.val_fields[0] =
+          mz_gpu_field{MZ_SRC_VAL_STREAM, 0, (u8)vb, 0, 0, 0, 0};
+    cl.out.key_words = kw;
+    cl.out.val_bytes = vb;
+  }
+  mz_gpu_temporal *op = new mz_gpu_temporal();
+  op->cl = cl;
+  op->tb.n = spec->n_bounds;
+  for (u32 i = 0; i < spec->n_bounds; i++) op->tb.b[i] = spec->bounds[i];
+  op->tb.until = spec->until;
+  op->kw = kw;
+  op->vb = vb;
+  // 64K rows by default; grows on demand
+  op->cap = spec->initial_rows ? spec->initial_rows : (1ull << 16);
+  op->held = flat_alloc(ctx, op->cap, cl.out.key_words, cl.out.val_bytes);
+  ctx->temporals.push_back(op);
+  return op;
+}
+
+void mz_gpu_temporal_drop(mz_gpu_ctx *c, mz_gpu_temporal *op) {
+  auto &v = c->impl.temporals;
+  v.erase(std::remove(v.begin(), v.end(), op), v.end());
+  temporal_free(&c->impl, op);
+}
+
+int mz_gpu_temporal_stats(mz_gpu_ctx *, mz_gpu_temporal *op,
+                          uint64_t *held_rows, uint64_t *next_time,
+                          uint64_t *frontier) {
+  *held_rows = op->n_held;
+  *next_time = op->min_time;
+  *frontier = op->started ? op->frontier : ~0ull;
+  return 0;
+}
+
+// One push. Nothing of the operator's state is written before the input is
+// known to be good: the kernels fill fresh queues (or the free tail of the
+// held buffer), and the held buffer, its mirrors and the frontier change
+// after the counter readback only.
+//   stage -> k_temporal_eval -> k_temporal_release (if a held time is below
+//   upper) -> counter readback -> consolidate ready rows (the out-batch) ->
+//   consolidate held-kept + held-new (the new held buffer) -> closing
+//   readback of its row count and smallest time -> error stream.
+static int temporal_push_impl(Ctx *ctx, mz_gpu_temporal *op,
+                              const mz_gpu_updates *u, mz_gpu_out **out) {
+  if (is_varlen(op->vb) || u->val_offs) {
+    ctx->err = "temporal: varlen updates unsupported";
+    return 1;
+  }
+  if (op->started && u->lower != op->frontier) {
+    ctx->err = "temporal: delta.lower " + std::to_string(u->lower) +
+               " is not the operator's frontier " +
+               std::to_string(op->frontier);
+    return 1;
+  }
+  if (u->upper < u->lower) {
+    ctx->err = "temporal: delta.upper is before delta.lower";
+    return 1;
+  }
+  (*ctx->scr).reset();
+  const mz_gpu_closure &cl = op->cl;
+  u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  u64 n = u->n, upper = u->upper;
+  // the common case of a far-future window: no held time is due
+  bool release = op->n_held && op->min_time < upper;
+  auto advance = [&]() {
+    op->started = true;
+    op->frontier = upper;
+  };
+  if (n == 0 && !release) {  // a tick that releases nothing
+    *out = empty_out(ctx, okw, ovb);
+    advance();
+    return 0;
+  }
+  if (op->n_held + 2 * n >= (1ull << 32)) {
+    ctx->err = "temporal: held rows + 2 * delta rows must stay below 2^32";
+    return 1;
+  }
+  // grow the held buffer to take this push's 2n rows behind what it holds
+  if (op->n_held + 2 * n > op->cap) {
+    u64 ncap = std::max<u64>(op->n_held + 2 * n, 2 * op->cap);
+    FlatCols g = flat_alloc(ctx, ncap, okw, ovb);
+    u64 m = op->n_held;
+    if (m) {
+      HIP_CHECK(hipMemcpyAsync(g.keys, op->held.keys, m * okw * 8,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+      if (ovb)
+        HIP_CHECK(hipMemcpyAsync(g.vals, op->held.vals, m * ovb,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(g.times, op->held.times, m * 8,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(g.diffs, op->held.diffs, m * 8,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    flat_free(ctx, op->held);
+    op->held = g;
+    op->cap = ncap;
+  }
+  // Queues at their exact bounds. Without a release pass the new held rows
+  // go behind the resident ones, in place; with one, kept and new rows
+  // both go to a fresh buffer.
+  FlatCols work = release ? flat_alloc(ctx, op->cap, okw, ovb) : op->held;
+  u64 held0 = release ? 0 : op->n_held;
+  HeldQueue hq{op->cap, work.keys, work.vals, work.times, work.diffs};
+  ProbeQueue pq{okw, ovb};
+  pq.alloc(ctx, std::max<u64>(2 * n + (release ? op->n_held : 0), 1),
+           std::max<u64>(n, 1));
+  u64 *ctr = (u64 *)(*ctx->scr).get(8 * 6);
+  pq.q.ctr = (unsigned long long *)ctr;
+  // [0] ready [1] errors [2] held [3] bad input times; the closing
+  // readback's [4] held rows after consolidation [5] their smallest time
+  fill_u64(ctx, ctr, 5, 0);
+  fill_u64(ctx, ctr + 2, 1, held0);
+  fill_u64(ctx, ctr + 5, 1, ~0ull);
+  if (n) {
+    DevUpdates d = stage_updates(ctx, u, op->kw, op->vb);
+    DeltaView dv{d.keys, op->vb ? d.vals : nullptr, op->vb, d.times, d.diffs,
+                 n, op->kw};
+    if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_a, ctx->stream));
+    hipLaunchKernelGGL(k_temporal_eval, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, dv, u->lower, upper, cl, op->tb, pq.q,
+                       hq);
+    if (ctx->time_kernels) HIP_CHECK(hipEventRecord(ctx->ev_b, ctx->stream));
+  }
+  if (release)
+    hipLaunchKernelGGL(k_temporal_release, dim3(ngrid(op->n_held)),
+                       dim3(BLK), 0, ctx->stream, op->held.keys,
+                       op->held.vals, op->held.times, op->held.diffs,
+                       op->n_held, okw, ovb, upper, pq.q, hq);
+  u64 h[4];
+  memcpy(h, d2h_pinned(ctx, ctr, 8 * 4), sizeof h);
+  u64 R = h[0], E = h[1], H = h[2], bad = h[3];
+  if (n && ctx->time_kernels) {  // the readback synced
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b));
+    ctx->probe_ms += ms;
+    ctx->probe_rows += n;
+    ctx->probe_launches += 1;
+  }
+  if (bad) {  // state untouched: only free memory was written
+    pq.free(ctx);
+    if (release) flat_free(ctx, work);
+    ctx->err = "temporal: " + std::to_string(bad) +
+               " input times outside [delta.lower, delta.upper)";
+    return 1;
+  }
+  // the out-batch: everything below upper, from this delta and from held
+  if (R) {
+    DevUpdates rin{pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, R};
+    u64 Rc;
+    FlatCols o = consolidate_dev(ctx, okw, ovb, rin, &Rc);
+    *out = make_out(o, Rc, okw, ovb);
+  } else {
+    *out = empty_out(ctx, okw, ovb);
+  }
+  pq.free_ok(ctx);
+  // the new held buffer. Without a release pass and without new held rows
+  // it is the old one, untouched.
+  if (release || H > held0) {
+    FlatCols nh = flat_alloc(ctx, op->cap, okw, ovb);
+    if (H) {
+      DevUpdates hin{work.keys, work.vals, work.times, work.diffs, H};
+      consolidate_core(ctx, okw, ovb, hin, nh, ctr + 4);
+      hipLaunchKernelGGL(k_time_min, dim3(ngrid(H)), dim3(BLK), 0,
+                         ctx->stream, nh.times, ctr + 4,
+                         (unsigned long long *)(ctr + 5));
+    }
+    memcpy(h, d2h_pinned(ctx, ctr + 4, 8 * 2), 16);  // the closing readback
+    if (release) flat_free(ctx, work);
+    flat_free(ctx, op->held);
+    op->held = nh;
+    op->n_held = h[0];
+    op->min_time = h[1];
+  }
+  attach_err_stream(ctx, *out, pq, E);
+  advance();
+  return 0;
+}
+
+int mz_gpu_temporal_push(mz_gpu_ctx *c, mz_gpu_temporal *op,
+                         const mz_gpu_updates *delta, mz_gpu_out **out) {
+  return temporal_push_impl(&c->impl, op, delta, out);
 }
 
 // Raw variant: output left unconsolidated (consumer consolidates).

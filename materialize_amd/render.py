@@ -603,6 +603,57 @@ def render_peek(ctx, arr, plan: PeekPlan) -> PeekOp:
     return PeekOp(ctx, arr, plan)
 
 
+@dataclass
+class TemporalFilterPlan:
+    """An MFP with temporal predicates (MfpPlan { lower_bounds,
+    upper_bounds }, src/expr/src/linear.rs) over one stream: `spec` from
+    abi.temporal_spec, its bounds from abi.time_bound."""
+    spec: abi.TemporalSpec
+
+
+class TemporalFilterOp:
+    """MfpPlan::evaluate plus the hold-back a downstream arrange batcher
+    does in the reference: each push returns the updates below its upper,
+    consolidated, and the operator keeps the future-stamped rest until the
+    frontier passes it. Every output time lies in the push's [lower,
+    upper)."""
+
+    def __init__(self, ctx, plan: TemporalFilterPlan):
+        if not getattr(ctx, "supports_temporal_filter", False):
+            raise NotImplementedError(
+                "this context does not implement the temporal filter")
+        self.ctx = ctx
+        self.op = ctx.temporal_create(plan.spec)
+
+    def push(self, updates) -> DevOut:
+        return self.ctx.temporal_push_dev(self.op, updates)
+
+    def advance(self, upper) -> DevOut:
+        """The frontier tick: an empty delta from the operator's own
+        frontier to `upper`; releases the expirations below `upper`."""
+        _, _, f = self.stats()
+        if f == 2**64 - 1:
+            raise ValueError("TemporalFilterOp.advance before the first "
+                             "push: the operator has no frontier yet")
+        empty = abi.make_updates(np.empty(0, np.int64), None,
+                                 np.empty(0, np.uint64),
+                                 np.empty(0, np.int64), f, upper)
+        return self.push(empty)
+
+    def stats(self):
+        """(held rows, smallest held time, frontier)."""
+        return self.ctx.temporal_stats(self.op)
+
+    def drop(self):
+        if self.op is not None:
+            self.ctx.temporal_drop(self.op)
+            self.op = None
+
+
+def render_temporal_filter(ctx, plan: TemporalFilterPlan) -> TemporalFilterOp:
+    return TemporalFilterOp(ctx, plan)
+
+
 def render_delta_join(ctx, arrangements, plan, exchange=None) -> DeltaJoinOp:
     return DeltaJoinOp(ctx, arrangements, plan, exchange=exchange)
 
