@@ -2436,6 +2436,9 @@ struct mz_gpu_join {
 // it from the push's closing readback to decide growth before the next
 // push. A host-counted table (minmax levels) has no device words and keeps
 // its count in n_rows alone.
+// Invariant: st.capacity is a power of two >= 16 and st.slots == 2 *
+// capacity, because every probe sequence masks with slots - 1. kt_create_at
+// rounds the requested capacity up; kt_compact_grow only doubles.
 struct KeyedTable {
   RedState st{};
   u32 kw = 0;              // key words; a hash slot is kw + 1 words
@@ -2690,12 +2693,16 @@ u64 exclusive_scan_u32(Ctx *c, const u32 *in, u32 *out, u64 n);
 
 // ---- keyed-table lifecycle (struct KeyedTable; protocol: DESIGN.md §4a)
 
-// Create a table of `cap` rows of [key kw][payload_w words] whose counters
-// live where the caller says: words of an operator-owned block, or nullptr
-// for a host-counted table. The hash is filled with the ~0 sentinel by a
-// kernel (never a memset, see fill_u64).
+// Create a table of at least `want` rows of [key kw][payload_w words] whose
+// counters live where the caller says: words of an operator-owned block, or
+// nullptr for a host-counted table. The request is rounded up to a power of
+// two, floor 16 (KeyedTable's capacity invariant): it may come straight from
+// an environment knob. The hash is filled with the ~0 sentinel by a kernel
+// (never a memset, see fill_u64).
 static void kt_create_at(Ctx *c, KeyedTable &T, u32 kw, u32 payload_w,
-                         u64 cap, u64 *d_nrows, u64 *d_err) {
+                         u64 want, u64 *d_nrows, u64 *d_err) {
+  u64 cap = 16;
+  while (cap < want) cap *= 2;
   T.kw = kw;
   T.n_rows = 0;
   T.d_nrows = d_nrows;
@@ -2724,10 +2731,13 @@ static void kt_free(Ctx *c, KeyedTable &T) {
   T = KeyedTable();
 }
 
-// Initial capacity: the operator's default unless the env names one.
+// Initial capacity: the operator's default unless the env names one (a
+// negative or unparsable value asks for the floor; kt_create_at rounds).
 static u64 kt_env_cap(const char *env, u64 dflt) {
   const char *e = getenv(env);
-  return e ? (u64)atoll(e) : dflt;
+  if (!e) return dflt;
+  long long v = atoll(e);
+  return v > 0 ? (u64)v : 0;
 }
 
 // Reclaim dead rows (all payload words zero) and grow the table so `need`
@@ -6756,10 +6766,8 @@ mz_gpu_collation *mz_gpu_collation_create(mz_gpu_ctx *c,
         c, &mm_in, op->mm_aggs[j].func == MZ_AGG_MAX_I64, spec->buckets,
         spec->n_levels));
   // 1M keys default; grows on demand; env override for tests/tuning
-  u64 want = kt_env_cap("MZ_GPU_COL_CAP", 1ull << 20);
-  u64 cap = 16;  // the hash masks with slots - 1: keep a power of two
-  while (cap < want) cap *= 2;
-  kt_create(ctx, op->tbl, kw, 1 + L.PW, cap, /*n_err=*/2);
+  kt_create(ctx, op->tbl, kw, 1 + L.PW,
+            kt_env_cap("MZ_GPU_COL_CAP", 1ull << 20), /*n_err=*/2);
   ctx->cols.push_back(op);
   return op;
 }

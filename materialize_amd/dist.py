@@ -15,10 +15,10 @@ diff) in one `all_to_all_single` with split sizes — the columnar
 import numpy as np
 
 
-def shard_of(keys, kw, world):
+def route_hash(keys, kw):
     """Vectorized splitmix64 route hash (matches mz_gpu_route_hash /
-    orc_route_hash exactly) -> shard ids."""
-    keys = keys.view(np.uint64).reshape(-1, kw)
+    orc_route_hash exactly) -> the raw u64 hash per key row."""
+    keys = np.ascontiguousarray(keys).view(np.uint64).reshape(-1, kw)
     h = np.full(len(keys), 0x9E3779B97F4A7C15, np.uint64)
     with np.errstate(over="ignore"):
         for w in range(kw):
@@ -29,7 +29,12 @@ def shard_of(keys, kw, world):
             x *= np.uint64(0x94D049BB133111EB)
             x ^= x >> np.uint64(31)
             h = x
-    return (h % np.uint64(world)).astype(np.int64)
+    return h
+
+
+def shard_of(keys, kw, world):
+    """Shard ids: route_hash(key) % world."""
+    return (route_hash(keys, kw) % np.uint64(world)).astype(np.int64)
 
 
 def pack_records(keys, vals, times, diffs, kw, vb):

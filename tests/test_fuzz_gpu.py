@@ -7,13 +7,28 @@ that the structured dataflow tests never produce."""
 import numpy as np
 import pytest
 
+import valdomain as vd
 from materialize_amd import _abi as abi
 
 pytestmark = pytest.mark.gpu
 
 
-def rand_batch(rng, t, nkeys, vb, n):
-    keys = rng.integers(-4, nkeys, (n, 1)).astype(np.int64)
+def small_keys(rng, lo, hi, n):
+    """Keys lo..hi-1: the schedule's original key source."""
+    return rng.integers(lo, hi, (n, 1)).astype(np.int64)
+
+
+def wrap_keys(rng, lo, hi, n):
+    """As many distinct keys, all of the hash class that starts in the
+    last three slots of every table of <= 4096 slots (valdomain.wrap_keys):
+    every batch table, and every keyed table that starts small, holds one
+    cluster that wraps around its end."""
+    pool = vd.wrap_keys(1)[:hi - lo]
+    return pool[rng.integers(0, hi - lo, n)].reshape(n, 1)
+
+
+def rand_batch(rng, t, nkeys, vb, n, keys_of=small_keys):
+    keys = keys_of(rng, -4, nkeys, n)
     vals = rng.integers(0, 4, (n, vb)).astype(np.uint8) if vb else None
     diffs = rng.integers(-2, 3, n).astype(np.int64)
     return abi.make_updates(keys, vals, np.full(n, t, np.uint64), diffs,
@@ -27,6 +42,19 @@ def assert_same(rg, ro, label):
 
 @pytest.mark.parametrize("seed", [101, 103, 107])
 def test_mixed_op_schedule(seed):
+    run_schedule(seed, small_keys)
+
+
+@pytest.mark.parametrize("keys_of", [wrap_keys], ids=["wrap"])
+@pytest.mark.parametrize("seed", [109])
+def test_mixed_op_schedule_key_source(seed, keys_of, monkeypatch):
+    # small keyed tables: the reduce and threshold tables grow under load
+    monkeypatch.setenv("MZ_GPU_RED_CAP", "32")
+    monkeypatch.setenv("MZ_GPU_THR_CAP", "64")
+    run_schedule(seed, keys_of)
+
+
+def run_schedule(seed, keys_of):
     from materialize_amd._ffi import GpuCtx
     from pyoracle import OracleCtx
     g, o = GpuCtx(), OracleCtx()
@@ -52,7 +80,7 @@ def test_mixed_op_schedule(seed):
         op = sched_rng.integers(0, 6)
         a = int(sched_rng.integers(0, n_arrs))
         n = int(sched_rng.integers(1, 800))
-        u = rand_batch(rng, t, 60, VB, n)
+        u = rand_batch(rng, t, 60, VB, n, keys_of)
         if op == 0:  # async insert (flushed by the next probe or sync)
             g.arr_insert_async(garrs[a], u)
             o.arr_insert_async(oarrs[a], u)
@@ -73,14 +101,14 @@ def test_mixed_op_schedule(seed):
             # topk requires non-negative accumulated multiplicities:
             # feed insert-only batches
             ku = abi.make_updates(
-                rng.integers(0, 30, (n, 1)).astype(np.int64),
+                keys_of(rng, 0, 30, n),
                 rng.integers(0, 3, (n, VB)).astype(np.uint8),
                 np.full(n, t, np.uint64), np.ones(n, np.int64), t, t + 1)
             assert_same(g.topk_push(gtk, ku), o.topk_push(otk, ku),
                         f"t{t} topk")
     # end-state check: every arrangement drained through a final probe
     for a in range(n_arrs):
-        pu = rand_batch(rng, 24, 60, VB, 500)
+        pu = rand_batch(rng, 24, 60, VB, 500, keys_of)
         assert_same(g.halfjoin(garrs[a], pu, VB, True, cl),
                     o.halfjoin(oarrs[a], pu, VB, True, cl),
                     f"final probe arr{a}")

@@ -8,17 +8,7 @@ import pytest
 
 from materialize_amd import _abi as abi
 from pyoracle import OracleCtx
-
-
-def canon_val_key(vb_bytes):
-    """The engine's canonical val order: zero-padded LE u64 words,
-    unsigned ascending (oracle.cpp cmp_val)."""
-    b = bytes(vb_bytes)
-    words = []
-    for off in range(0, len(b), 8):
-        chunk = b[off:off + 8] + bytes(8 - min(8, len(b) - off))
-        words.append(int.from_bytes(chunk, "little"))
-    return tuple(words)
+from valdomain import canon_val_key
 
 
 def naive_topk_output(counts, order, offset, limit):
