@@ -565,8 +565,9 @@ int  mz_gpu_peek_scan(mz_gpu_ctx *ctx, mz_gpu_arr *arr, uint64_t as_of,
  *  4. Otherwise (proj(row), lo, d) unless lo >= until, and, if hi exists and
  *     hi < until, (proj(row), hi, -d); the negation wraps, as Diff does.
  * Unlike the reference, the projection may not contain a field that can
- * error (MZ_COMPUTE_DIV_I64): put it in a following map
- * call. Bound errors are emitted at the input time and are never held.
+ * error (MZ_COMPUTE_DIV_I64): put the division in a following
+ * mz_gpu_mfp program, whose out-batch has the error stream for it (that of
+ * mz_gpu_map has none). Bound errors are emitted at the input time and are never held.
  *
  * Frontier and hold-back. The -d update usually lies in the future, beyond
  * the batch's upper. Timely lets such updates travel and the downstream
@@ -621,6 +622,113 @@ int  mz_gpu_temporal_stats(mz_gpu_ctx *ctx, mz_gpu_temporal *op,
                            uint64_t *frontier);
 void mz_gpu_temporal_drop(mz_gpu_ctx *ctx, mz_gpu_temporal *op);
 enum { MZ_ERR_TIMESTAMP_OUT_OF_RANGE = 2 };
+
+/* ------------------------------------------- scalar-expression MFP
+ * Replaces the non-temporal half of MapFilterProject: SafeMfpPlan::evaluate
+ * (src/expr/src/linear.rs) over MirScalarExpr trees — BinaryFunc::eval,
+ * UnaryFunc::eval, VariadicFunc::And / Or / Coalesce, MirScalarExpr::If
+ * (src/expr/src/scalar.rs, scalar/func.rs) — for the integer and boolean
+ * datums this engine carries. A stateless stream operator: it sits before
+ * or after any join, reduce or temporal filter. This is where a division
+ * that the temporal filter's projection refuses goes (mz_gpu_map has no
+ * error stream: do not put a field that can error there).
+ *
+ * The program is postfix over a value stack of at most MZ_GPU_XSTACK
+ * entries. Pushes: COL, LIT, NULL. Unary: NEG ABS NOT IS_NULL. Binary
+ * (left operand pushed first): ADD SUB MUL DIV MOD, LT LE GT GE EQ NE,
+ * AND OR, COALESCE. Ternary: IF (cond, then, else pushed in that order).
+ * Statements pop one value and leave the stack empty: FILTER, OUT.
+ *
+ * Value model. A value is (i64, tag): tag 0 = datum, 1 = NULL,
+ * 1 + MZ_ERR_* = that error. Booleans are 0 / 1. COL sign-extends a 4- or
+ * 8-byte little-endian integer; a width-1 COL reads a boolean byte; with
+ * `nullable`, a nonzero byte at off + width makes the value NULL. Errors
+ * are values: every operator is evaluated eagerly, and an operator the
+ * reference evaluates lazily selects among its evaluated operands. As
+ * expressions are pure, that is the lazy semantics.
+ *
+ * Strict operators (arithmetic, comparisons, NEG, ABS, NOT), in this order:
+ * a left operand that is an error gives that error; else a right operand
+ * that is an error gives that error; else any NULL operand gives NULL; else
+ * the operator computes. (An error on the right beats a NULL on the left:
+ * both operands are evaluated before the NULL check.)
+ *   ADD SUB MUL  checked; overflow gives MZ_ERR_NUMERIC_FIELD_OVERFLOW.
+ *   DIV          truncates toward zero; a zero divisor gives
+ *                MZ_ERR_DIVISION_BY_ZERO; INT64_MIN / -1 gives
+ *                MZ_ERR_INT64_OUT_OF_RANGE.
+ *   MOD          a zero divisor gives MZ_ERR_DIVISION_BY_ZERO; the sign
+ *                follows the dividend; INT64_MIN % -1 = 0.
+ *   NEG ABS      of INT64_MIN give MZ_ERR_INT64_OUT_OF_RANGE.
+ * AND: either operand a definite false gives false; else an operand that is
+ * an error gives that error (the left one first); else either operand NULL
+ * gives NULL; else true. OR is the dual on true. (When both operands error
+ * with different codes the reference takes the larger EvalError; this takes
+ * the left one — DESIGN.md §2.9.)
+ * IS_NULL: an error stays an error; otherwise 0 / 1.
+ * IF: an error condition is that error; a true condition gives the
+ * then-value; a false or NULL condition the else-value. The value not taken
+ * is discarded, errors included.
+ * COALESCE(a, b): b when a is NULL, otherwise a (an error a included).
+ * N-ary COALESCE / AND / OR are built by right-nesting.
+ *
+ * Statements run in program order; the first decisive one wins, and later
+ * statements of a dropped or errored row have no effect.
+ *   FILTER  an error makes the row the error row (code, time, diff) in the
+ *           out-batch's error stream; false or NULL drops the row.
+ *   OUT     the first matching rule decides: an error value makes the row
+ *           an error row; a NULL into a non-nullable field gives
+ *           MZ_ERR_UNEXPECTED_NULL; a width-4 store of a value outside i32
+ *           gives MZ_ERR_INT32_OUT_OF_RANGE; otherwise the datum is stored.
+ *           A NULL into a nullable field stores zero datum bytes and null
+ *           byte 1 (canonical: byte-equal consolidation stays exact); a
+ *           datum into a nullable field stores null byte 0.
+ *
+ * Refused (non-zero return, message in mz_gpu_last_error): n_ops >
+ * MZ_GPU_MAX_XOPS; an unknown opcode; a stack that goes below 0 or above
+ * MZ_GPU_XSTACK, is not empty after a statement or at the end; a COL of a
+ * source other than MZ_SRC_KEY / MZ_SRC_VAL_STREAM, of width other than 1,
+ * 4, 8, or reading past the input key or val (the null byte included); OUT
+ * fields that do not tile the out key and the out val exactly (every byte
+ * written once: no gap, no overlap); a key OUT that is not width 8 and
+ * non-nullable; a varlen schema; a schema, in or out, outside 1..2 key
+ * words and 0..64 val bytes.
+ *
+ * Out-batch: one row per passing input row, at the input's time and diff.
+ * consolidate != 0: consolidated, in canonical order. consolidate == 0: the
+ * raw rows in queue order, for a consolidating consumer. The error rows are
+ * always consolidated. */
+enum {
+  MZ_X_COL = 0, MZ_X_LIT, MZ_X_NULL,
+  MZ_X_NEG, MZ_X_ABS, MZ_X_NOT, MZ_X_IS_NULL,
+  MZ_X_ADD, MZ_X_SUB, MZ_X_MUL, MZ_X_DIV, MZ_X_MOD,
+  MZ_X_LT, MZ_X_LE, MZ_X_GT, MZ_X_GE, MZ_X_EQ, MZ_X_NE,
+  MZ_X_AND, MZ_X_OR, MZ_X_COALESCE,
+  MZ_X_IF,
+  MZ_X_FILTER, MZ_X_OUT
+};
+enum { MZ_ERR_INT64_OUT_OF_RANGE = 3,
+       MZ_ERR_NUMERIC_FIELD_OVERFLOW = 4,
+       MZ_ERR_INT32_OUT_OF_RANGE = 5,
+       MZ_ERR_UNEXPECTED_NULL = 6 };
+#define MZ_GPU_MAX_XOPS 64
+#define MZ_GPU_XSTACK   8
+typedef struct {            /* 16 bytes */
+  uint8_t  op;              /* MZ_X_* */
+  uint8_t  src;             /* COL: MZ_SRC_KEY | MZ_SRC_VAL_STREAM; OUT: 0 = key, 1 = val */
+  uint8_t  width;           /* COL / OUT: 1, 4 or 8 */
+  uint8_t  nullable;        /* COL / OUT: null-indicator byte at off + width */
+  uint16_t off;             /* COL / OUT: byte offset */
+  uint16_t pad;
+  int64_t  imm;             /* LIT */
+} mz_gpu_xop;
+typedef struct {
+  uint32_t n_ops;
+  mz_gpu_xop ops[MZ_GPU_MAX_XOPS];
+  mz_gpu_schema in, out;
+} mz_gpu_mfp_spec;
+int  mz_gpu_mfp(mz_gpu_ctx *ctx, const mz_gpu_mfp_spec *spec,
+                const mz_gpu_updates *updates, int consolidate,
+                mz_gpu_out **out);
 
 /* The routing hash itself (host helper; device code uses the same). */
 uint64_t mz_gpu_route_hash(const uint64_t *key_words, uint32_t n_words);

@@ -552,3 +552,272 @@ def temporal_spec(in_schema, bounds, mfp=None, until=None, initial_rows=0):
     sp.until = 0xFFFFFFFFFFFFFFFF if until is None else until
     sp.initial_rows = initial_rows
     return sp
+
+
+# ------------------------------------------------- scalar-expression MFP
+# mz_gpu_mfp: a postfix expression program over one update stream
+# (include/mz_gpu.h states the semantics).
+(MZ_X_COL, MZ_X_LIT, MZ_X_NULL, MZ_X_NEG, MZ_X_ABS, MZ_X_NOT, MZ_X_IS_NULL,
+ MZ_X_ADD, MZ_X_SUB, MZ_X_MUL, MZ_X_DIV, MZ_X_MOD, MZ_X_LT, MZ_X_LE, MZ_X_GT,
+ MZ_X_GE, MZ_X_EQ, MZ_X_NE, MZ_X_AND, MZ_X_OR, MZ_X_COALESCE, MZ_X_IF,
+ MZ_X_FILTER, MZ_X_OUT) = range(24)
+MZ_ERR_INT64_OUT_OF_RANGE = 3
+MZ_ERR_NUMERIC_FIELD_OVERFLOW = 4
+MZ_ERR_INT32_OUT_OF_RANGE = 5
+MZ_ERR_UNEXPECTED_NULL = 6
+MZ_GPU_MAX_XOPS = 64
+MZ_GPU_XSTACK = 8
+
+
+class XOp(C.Structure):
+    """mz_gpu_xop: one postfix instruction."""
+    _fields_ = [
+        ("op", C.c_uint8),
+        ("src", C.c_uint8),
+        ("width", C.c_uint8),
+        ("nullable", C.c_uint8),
+        ("off", C.c_uint16),
+        ("pad", C.c_uint16),
+        ("imm", C.c_int64),
+    ]
+
+
+class MfpSpec(C.Structure):
+    """mz_gpu_mfp_spec: the program and the schemas it maps between."""
+    _fields_ = [
+        ("n_ops", C.c_uint32),
+        ("ops", XOp * MZ_GPU_MAX_XOPS),
+        ("in_", Schema),
+        ("out", Schema),
+    ]
+
+
+_X_ARITH = (MZ_X_ADD, MZ_X_SUB, MZ_X_MUL, MZ_X_DIV, MZ_X_MOD)
+_X_CMP = (MZ_X_LT, MZ_X_LE, MZ_X_GT, MZ_X_GE, MZ_X_EQ, MZ_X_NE)
+
+
+class Expr:
+    """A scalar expression tree with a type, "int" or "bool". Leaves come
+    from x_col / x_lit / x_null; Python operators and x_abs / x_is_null /
+    x_if / x_coalesce build the rest and check operand types (ValueError).
+    `==` and `!=` build comparisons, so trees are compared by identity."""
+
+    def __init__(self, op, typ, args=(), src=0, off=0, width=0, nullable=0,
+                 imm=0):
+        self.op, self.typ, self.args = op, typ, tuple(args)
+        self.src, self.off, self.width = src, off, width
+        self.nullable, self.imm = nullable, imm
+
+    __hash__ = object.__hash__
+
+    def _bin(self, op, other, swap=False):
+        a, b = x_expr(self), x_expr(other)
+        if swap:
+            a, b = b, a
+        if op in (MZ_X_AND, MZ_X_OR):
+            want, typ = "bool", "bool"
+        else:
+            want, typ = "int", ("int" if op in _X_ARITH else "bool")
+        for e in (a, b):
+            if e.typ != want:
+                raise ValueError(f"mfp: operator {op} takes {want} operands, "
+                                 f"got {e.typ}")
+        return Expr(op, typ, (a, b))
+
+    def __add__(self, o): return self._bin(MZ_X_ADD, o)
+    def __radd__(self, o): return self._bin(MZ_X_ADD, o, True)
+    def __sub__(self, o): return self._bin(MZ_X_SUB, o)
+    def __rsub__(self, o): return self._bin(MZ_X_SUB, o, True)
+    def __mul__(self, o): return self._bin(MZ_X_MUL, o)
+    def __rmul__(self, o): return self._bin(MZ_X_MUL, o, True)
+    def __floordiv__(self, o): return self._bin(MZ_X_DIV, o)
+    def __rfloordiv__(self, o): return self._bin(MZ_X_DIV, o, True)
+    def __mod__(self, o): return self._bin(MZ_X_MOD, o)
+    def __rmod__(self, o): return self._bin(MZ_X_MOD, o, True)
+    def __lt__(self, o): return self._bin(MZ_X_LT, o)
+    def __le__(self, o): return self._bin(MZ_X_LE, o)
+    def __gt__(self, o): return self._bin(MZ_X_GT, o)
+    def __ge__(self, o): return self._bin(MZ_X_GE, o)
+    def __eq__(self, o): return self._bin(MZ_X_EQ, o)
+    def __ne__(self, o): return self._bin(MZ_X_NE, o)
+    def __and__(self, o): return self._bin(MZ_X_AND, o)
+    def __rand__(self, o): return self._bin(MZ_X_AND, o, True)
+    def __or__(self, o): return self._bin(MZ_X_OR, o)
+    def __ror__(self, o): return self._bin(MZ_X_OR, o, True)
+
+    def _un(self, op, want, typ):
+        if want is not None and self.typ != want:
+            raise ValueError(f"mfp: operator {op} takes a {want} operand, "
+                             f"got {self.typ}")
+        return Expr(op, typ, (self,))
+
+    def __neg__(self): return self._un(MZ_X_NEG, "int", "int")
+    def __invert__(self): return self._un(MZ_X_NOT, "bool", "bool")
+
+    def __bool__(self):
+        raise TypeError("an mfp Expr has no truth value; use & | ~")
+
+
+def x_expr(v):
+    """An Expr as it is; a Python bool or int as a literal."""
+    return v if isinstance(v, Expr) else x_lit(v)
+
+
+def x_col(src, off, width=8, nullable=0):
+    """The input row's datum at (src, off): a 4- or 8-byte signed LE integer,
+    or (width 1) a boolean byte; `nullable` = a null byte follows it."""
+    if width not in (1, 4, 8):
+        raise ValueError("mfp: column width must be 1, 4 or 8")
+    return Expr(MZ_X_COL, "bool" if width == 1 else "int", src=src, off=off,
+                width=width, nullable=1 if nullable else 0)
+
+
+def x_lit(v):
+    if isinstance(v, (bool, np.bool_)):
+        return Expr(MZ_X_LIT, "bool", imm=int(v))
+    v = int(v)
+    if not -2**63 <= v < 2**63:
+        raise ValueError(f"mfp: literal {v} is not an i64")
+    return Expr(MZ_X_LIT, "int", imm=v)
+
+
+def x_null(typ):
+    if typ not in ("int", "bool"):
+        raise ValueError(f"mfp: unknown type {typ!r}")
+    return Expr(MZ_X_NULL, typ)
+
+
+def x_abs(e):
+    return x_expr(e)._un(MZ_X_ABS, "int", "int")
+
+
+def x_is_null(e):
+    return x_expr(e)._un(MZ_X_IS_NULL, None, "bool")
+
+
+def x_if(cond, then, els):
+    cond, then, els = x_expr(cond), x_expr(then), x_expr(els)
+    if cond.typ != "bool":
+        raise ValueError("mfp: the IF condition must be bool")
+    if then.typ != els.typ:
+        raise ValueError("mfp: the IF branches differ in type")
+    return Expr(MZ_X_IF, then.typ, (cond, then, els))
+
+
+def x_coalesce(first, *rest):
+    """COALESCE(first, *rest), right-nested."""
+    es = [x_expr(first)] + [x_expr(r) for r in rest]
+    if any(e.typ != es[0].typ for e in es):
+        raise ValueError("mfp: the COALESCE arguments differ in type")
+    acc = es[-1]
+    for e in reversed(es[:-1]):
+        acc = Expr(MZ_X_COALESCE, e.typ, (e, acc))
+    return acc
+
+
+class XStmt:
+    """FILTER or OUT: a statement of an mfp program."""
+
+    def __init__(self, op, expr, src=0, off=0, width=0, nullable=0):
+        self.op, self.expr = op, x_expr(expr)
+        self.src, self.off, self.width = src, off, width
+        self.nullable = 1 if nullable else 0
+
+
+def x_filter(e):
+    return XStmt(MZ_X_FILTER, e)
+
+
+def x_out_key(e, off):
+    return XStmt(MZ_X_OUT, e, src=0, off=off, width=8)
+
+
+def x_out_val(e, off, width, nullable=0):
+    return XStmt(MZ_X_OUT, e, src=1, off=off, width=width, nullable=nullable)
+
+
+def _x_emit(e, ops):
+    """Postfix: operands left to right, then the operator."""
+    for a in e.args:
+        _x_emit(a, ops)
+    ops.append(XOp(op=e.op, src=e.src, width=e.width, nullable=e.nullable,
+                   off=e.off, imm=e.imm))
+
+
+def mfp_spec(in_schema, out_schema, statements):
+    """mz_gpu_mfp_spec for `statements` (x_filter / x_out_key / x_out_val
+    items, run in the given order) over rows of `in_schema`, producing rows
+    of `out_schema`. Checks the statements' types and every create-time rule
+    of the C layer (ValueError)."""
+    for s in (in_schema, out_schema):
+        if s.val_bytes == MZ_GPU_VARLEN:
+            raise ValueError("mfp: varlen schemas unsupported")
+        if not 1 <= s.key_words <= MAX_KW or s.val_bytes > MAX_VB:
+            raise ValueError("mfp: schemas must have 1..2 key words and at "
+                             "most 64 val bytes")
+    ops = []
+    for i, st in enumerate(statements):
+        if st.op == MZ_X_FILTER:
+            if st.expr.typ != "bool":
+                raise ValueError(f"mfp: statement {i}: FILTER takes a bool")
+        else:
+            if st.width not in (1, 4, 8):
+                raise ValueError(f"mfp: statement {i}: OUT width must be 1, "
+                                 "4 or 8")
+            if (st.width == 1) != (st.expr.typ == "bool"):
+                raise ValueError(f"mfp: statement {i}: width 1 is for bool "
+                                 "values and only for them")
+            if st.src == 0 and (st.width != 8 or st.nullable):
+                raise ValueError(f"mfp: statement {i}: a key OUT is 8 bytes "
+                                 "wide and not nullable")
+        _x_emit(st.expr, ops)
+        ops.append(XOp(op=st.op, src=st.src, width=st.width,
+                       nullable=st.nullable, off=st.off))
+    if len(ops) > MZ_GPU_MAX_XOPS:
+        raise ValueError(f"mfp: the program has {len(ops)} ops, more than "
+                         f"{MZ_GPU_MAX_XOPS}")
+    room = (8 * in_schema.key_words, in_schema.val_bytes)
+    oroom = (8 * out_schema.key_words, out_schema.val_bytes)
+    written = ([0] * oroom[0], [0] * oroom[1])
+    arity = {MZ_X_COL: 0, MZ_X_LIT: 0, MZ_X_NULL: 0, MZ_X_NEG: 1,
+             MZ_X_ABS: 1, MZ_X_NOT: 1, MZ_X_IS_NULL: 1, MZ_X_IF: 3,
+             MZ_X_FILTER: 1, MZ_X_OUT: 1}
+    depth = 0
+    for i, op in enumerate(ops):
+        if op.op == MZ_X_COL:
+            if op.src not in (MZ_SRC_KEY, MZ_SRC_VAL_STREAM):
+                raise ValueError(f"mfp: op {i}: COL must read MZ_SRC_KEY or "
+                                 "MZ_SRC_VAL_STREAM")
+            if op.off + op.width + op.nullable > room[op.src]:
+                raise ValueError(f"mfp: op {i}: COL reads past the input "
+                                 "row's key or val")
+        depth -= arity.get(op.op, 2)
+        assert depth >= 0  # trees cannot underflow
+        if op.op in (MZ_X_FILTER, MZ_X_OUT):
+            assert depth == 0
+        else:
+            depth += 1
+        if depth > MZ_GPU_XSTACK:
+            raise ValueError(f"mfp: op {i}: the expression needs a stack "
+                             f"deeper than {MZ_GPU_XSTACK}")
+        if op.op != MZ_X_OUT:
+            continue
+        end = op.off + op.width + op.nullable
+        if end > oroom[op.src]:
+            raise ValueError(f"mfp: op {i}: OUT writes past the output "
+                             "row's key or val")
+        for b in range(op.off, end):
+            if written[op.src][b]:
+                raise ValueError(f"mfp: op {i}: OUT fields overlap")
+            written[op.src][b] = 1
+    for s, what in ((0, "key"), (1, "val")):
+        if not all(written[s]):
+            raise ValueError(f"mfp: OUT fields leave a gap in the output "
+                             f"{what}")
+    sp = MfpSpec()
+    sp.n_ops = len(ops)
+    for i, op in enumerate(ops):
+        sp.ops[i] = op
+    sp.in_ = in_schema
+    sp.out = out_schema
+    return sp

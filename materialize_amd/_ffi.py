@@ -8,8 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (Closure, CollationSpec, OutBatch, ReduceSpec, Schema,
-                   TemporalSpec, TopKSpec, Updates, out_to_numpy)
+from ._abi import (Closure, CollationSpec, MfpSpec, OutBatch, ReduceSpec,
+                   Schema, TemporalSpec, TopKSpec, Updates, out_to_numpy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "csrc", "libmzgpu.so")
@@ -156,6 +156,9 @@ def load():
     lib.mz_gpu_temporal_stats.argtypes = [C.c_void_p, C.c_void_p] + \
         [C.POINTER(C.c_uint64)] * 3
     lib.mz_gpu_temporal_drop.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mz_gpu_mfp.argtypes = [C.c_void_p, C.POINTER(MfpSpec),
+                               C.POINTER(Updates), C.c_int,
+                               C.POINTER(C.POINTER(OutBatch))]
     lib.mz_gpu_route_hash.restype = C.c_uint64
     lib.mz_gpu_route_hash.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
     lib.mz_gpu_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -179,6 +182,9 @@ class GpuCtx:
     # Temporal filters (mz_gpu_temporal_*) are implemented here;
     # render_temporal_filter refuses contexts that do not say so.
     supports_temporal_filter = True
+    # Scalar-expression MFPs (mz_gpu_mfp) are implemented here; render_mfp
+    # refuses contexts that do not say so.
+    supports_mfp = True
 
     def __init__(self, device=0):
         self.lib = load()
@@ -459,6 +465,21 @@ class GpuCtx:
     def temporal_drop(self, op):
         self.lib.mz_gpu_temporal_drop(self.ctx, op)
 
+    def _mfp(self, spec, upd, consolidate):
+        outp = C.POINTER(OutBatch)()
+        self._check(self.lib.mz_gpu_mfp(self.ctx, C.byref(spec),
+                                        C.byref(upd),
+                                        1 if consolidate else 0,
+                                        C.byref(outp)))
+        return outp
+
+    def mfp(self, spec, upd, consolidate=True):
+        """Run the expression program `spec` (abi.mfp_spec) over a stream:
+        host columns of the passing rows, consolidated and in canonical
+        order, or with consolidate=False raw, in queue order. Rows whose
+        evaluation errors land in self.last_errs."""
+        return self._take(self._mfp(spec, upd, consolidate))
+
     # --- device-resident variants (outputs stay on the GPU; used by the
     # render layer to chain stages without host round trips) ---
     def _dev_out(self, outp, sorted=False):
@@ -498,6 +519,10 @@ class GpuCtx:
     def temporal_push_dev(self, op, upd):
         # consolidated output in canonical order
         return self._dev_out(self._temporal_push(op, upd), sorted=True)
+
+    def mfp_dev(self, spec, upd, consolidate=True):
+        return self._dev_out(self._mfp(spec, upd, consolidate),
+                             sorted=bool(consolidate))
 
     def halfjoin_dev(self, lookup, upd, stream_vb, le, cl):
         # raw (unconsolidated) output: the render layer's consumers —

@@ -1023,6 +1023,236 @@ __global__ void k_temporal_release(const u64 *keys, const u8 *vals,
   }
 }
 
+// ------------------------------------------- scalar-expression MFP (device)
+// The postfix interpreter of mz_gpu_mfp_spec (mz_gpu.h states the
+// semantics). A value is (i64, tag): tag 0 datum, 1 NULL, 1 + MZ_ERR_* an
+// error. Everything is evaluated eagerly and the lazy operators select, so
+// the program counter, the stack pointer and the opcode switch are uniform
+// across the wave; only data differs between lanes.
+struct XVal {
+  i64 v;
+  u32 t;
+};
+#define XERR(code) (1u + (u32)(code))
+
+__device__ __forceinline__ XVal d_x_unary(u8 op, XVal a) {
+  if (a.t >= 2) return {0, a.t};
+  if (op == MZ_X_IS_NULL) return {(i64)(a.t == 1), 0};
+  if (a.t) return {0, 1};
+  if (op == MZ_X_NOT) return {(i64)(a.v == 0), 0};
+  if (a.v == INT64_MIN) return {0, XERR(MZ_ERR_INT64_OUT_OF_RANGE)};
+  return {(op == MZ_X_ABS && a.v >= 0) ? a.v : -a.v, 0};
+}
+
+__device__ __forceinline__ XVal d_x_binary(u8 op, XVal a, XVal b) {
+  if (op == MZ_X_COALESCE) return a.t == 1 ? b : a;
+  if (op == MZ_X_AND || op == MZ_X_OR) {
+    i64 dom = op == MZ_X_OR;  // the operand value that decides alone
+    if ((a.t == 0 && a.v == dom) || (b.t == 0 && b.v == dom)) return {dom, 0};
+    if (a.t >= 2) return {0, a.t};
+    if (b.t >= 2) return {0, b.t};
+    if (a.t | b.t) return {0, 1};
+    return {1 - dom, 0};
+  }
+  if (a.t >= 2) return {0, a.t};
+  if (b.t >= 2) return {0, b.t};
+  if (a.t | b.t) return {0, 1};
+  i64 x = a.v, y = b.v, r = 0;
+  switch (op) {
+    case MZ_X_ADD:
+      if (__builtin_add_overflow(x, y, &r))
+        return {0, XERR(MZ_ERR_NUMERIC_FIELD_OVERFLOW)};
+      break;
+    case MZ_X_SUB:
+      if (__builtin_sub_overflow(x, y, &r))
+        return {0, XERR(MZ_ERR_NUMERIC_FIELD_OVERFLOW)};
+      break;
+    case MZ_X_MUL:
+      if (__builtin_mul_overflow(x, y, &r))
+        return {0, XERR(MZ_ERR_NUMERIC_FIELD_OVERFLOW)};
+      break;
+    case MZ_X_DIV:
+    case MZ_X_MOD: {
+      if (y == 0) return {0, XERR(MZ_ERR_DIVISION_BY_ZERO)};
+      if (y == -1) {  // the one quotient that does not fit
+        if (op == MZ_X_MOD) return {0, 0};
+        if (x == INT64_MIN) return {0, XERR(MZ_ERR_INT64_OUT_OF_RANGE)};
+        return {-x, 0};
+      }
+      i64 q = x / y;  // truncates toward zero; y is neither 0 nor -1
+      r = op == MZ_X_DIV ? q : x - q * y;
+      break;
+    }
+    case MZ_X_LT: r = x < y; break;
+    case MZ_X_LE: r = x <= y; break;
+    case MZ_X_GT: r = x > y; break;
+    case MZ_X_GE: r = x >= y; break;
+    case MZ_X_EQ: r = x == y; break;
+    default: r = x != y; break;  // MZ_X_NE
+  }
+  return {r, 0};
+}
+
+// Run the program over one input row. The lane's stack is its column of
+// the block's LDS arrays: slot s lives at lv[s * BLK] / lt[s * BLK] (lv and
+// lt already offset by threadIdx.x), so a lane touches no other lane's
+// entries, consecutive lanes hit consecutive banks and no barrier is
+// needed. Returns the row's class: 0 dropped, 1 ok, 1 + MZ_ERR_* an error
+// row. STORE = false classifies only; STORE = true also writes the OUT
+// fields to okey / oval, and is run on rows classified ok.
+template <bool STORE>
+__device__ __forceinline__ u32 d_mfp_run(const mz_gpu_mfp_spec &P,
+                                         const u64 *key, const u8 *val,
+                                         u64 *okey, u8 *oval, i64 *lv,
+                                         u8 *lt) {
+  u32 cls = 1;
+  u32 sp = 0;  // uniform: create-time validation simulated it
+  auto pop = [&]() -> XVal {
+    sp--;
+    return {lv[sp * BLK], (u32)lt[sp * BLK]};
+  };
+  auto push = [&](XVal x) {
+    lv[sp * BLK] = x.v;
+    lt[sp * BLK] = (u8)x.t;
+    sp++;
+  };
+  for (u32 pc = 0; pc < P.n_ops; pc++) {
+    const mz_gpu_xop op = P.ops[pc];  // wave-uniform: scalar loads
+    switch (op.op) {
+      case MZ_X_COL: {
+        const u8 *p = (op.src == MZ_SRC_KEY ? (const u8 *)key : val) + op.off;
+        XVal x{0, 0};
+        if (op.nullable && p[op.width] != 0)
+          x.t = 1;
+        else if (op.width == 1)
+          x.v = p[0] != 0;
+        else
+          x.v = d_read_int(p, op.width);
+        push(x);
+        break;
+      }
+      case MZ_X_LIT: push({op.imm, 0}); break;
+      case MZ_X_NULL: push({0, 1}); break;
+      case MZ_X_NEG:
+      case MZ_X_ABS:
+      case MZ_X_NOT:
+      case MZ_X_IS_NULL: push(d_x_unary(op.op, pop())); break;
+      case MZ_X_IF: {
+        XVal e = pop(), t = pop(), c = pop();
+        push(c.t >= 2 ? XVal{0, c.t} : (c.t == 0 && c.v != 0) ? t : e);
+        break;
+      }
+      case MZ_X_FILTER: {
+        XVal x = pop();
+        if (cls == 1) {
+          if (x.t >= 2)
+            cls = x.t;
+          else if (x.t == 1 || x.v == 0)
+            cls = 0;
+        }
+        break;
+      }
+      case MZ_X_OUT: {
+        XVal x = pop();
+        if (!STORE) {
+          if (cls != 1) break;
+          if (x.t >= 2)
+            cls = x.t;
+          else if (x.t == 1 && !op.nullable)
+            cls = XERR(MZ_ERR_UNEXPECTED_NULL);
+          else if (x.t == 0 && op.width == 4 && x.v != (i64)(int32_t)x.v)
+            cls = XERR(MZ_ERR_INT32_OUT_OF_RANGE);
+          break;
+        }
+        u8 *dst = (op.src == 0 ? (u8 *)okey : oval) + op.off;
+        i64 v = x.t ? 0 : x.v;  // NULL: zero datum bytes
+        if (op.width == 8) {
+          memcpy(dst, &v, 8);
+        } else if (op.width == 4) {
+          int32_t w = (int32_t)v;
+          memcpy(dst, &w, 4);
+        } else {
+          dst[0] = (u8)v;
+        }
+        if (op.nullable) dst[op.width] = (u8)(x.t == 1);
+        break;
+      }
+      default: {  // the binary operators
+        XVal b = pop(), a = pop();
+        push(d_x_binary(op.op, a, b));
+        break;
+      }
+    }
+  }
+  return cls;
+}
+
+// Grid-stride over the input updates, as k_temporal_eval: every lane of a
+// wave runs the same number of iterations and reaches the one reservation
+// in each (row indices are clamped; idle lanes reserve nothing). A lane
+// takes MFP_ROWS rows per iteration, a grid stride apart, so that loads stay
+// coalesced: a classify pass without stores gives each row's class, the
+// wave reserves once for all of them — the counters are one address each
+// and returning atomics on one address serialise, so reservations, not
+// bytes, are what this kernel pays for — and then the ok rows
+// run the program again with OUT storing straight to the reserved slots and
+// the error rows write (code, time, diff). An input row yields at most one
+// row, in exactly one queue, so both queues are sized at the exact bound n:
+// nothing overflows and nothing is relaunched.
+#define MFP_ROWS 8
+__global__ void __launch_bounds__(BLK)
+    k_mfp_eval(DeltaView d, const mz_gpu_mfp_spec P, EmitQueue q) {
+  __shared__ i64 s_lv[MZ_GPU_XSTACK * BLK];
+  __shared__ u8 s_lt[MZ_GPU_XSTACK * BLK];
+  i64 *lv = s_lv + threadIdx.x;
+  u8 *lt = s_lt + threadIdx.x;
+  u32 okw = P.out.key_words, ovb = P.out.val_bytes;
+  u64 stride = (u64)gridDim.x * blockDim.x;
+  u64 start = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  u64 span = stride * MFP_ROWS;
+  u64 iters = (d.n + span - 1) / span;  // uniform across the wave
+  u32 lane = threadIdx.x & 63;
+  for (u64 it = 0; it < iters; it++) {
+    u64 base = start + it * span;
+    u32 classes = 0;  // 4 bits per row: 0 dropped, 1 ok, 1 + MZ_ERR_*
+    u32 c = 0, e = 0;
+#pragma unroll 1
+    for (u32 j = 0; j < MFP_ROWS; j++) {
+      u64 idx = base + j * stride;
+      if (idx - lane >= d.n) break;  // the whole wave is past the end
+      bool valid = idx < d.n;
+      const DeltaView::Row r = d.row(valid ? idx : d.n - 1);
+      u32 cls = d_mfp_run<false>(P, r.key, r.val, nullptr, nullptr, lv, lt);
+      if (!valid) cls = 0;
+      classes |= cls << (4 * j);
+      c += cls == 1;
+      e += cls >= 2;
+    }
+    u64 o, eo;
+    (void)q.reserve(c, e, lane, &o, &eo);
+    // the capacities are exact bounds; a slot past one is never written
+    if (o + c > q.cap || eo + e > q.ecap) continue;
+#pragma unroll 1
+    for (u32 j = 0; j < MFP_ROWS && (classes >> (4 * j)); j++) {
+      u32 cls = (classes >> (4 * j)) & 15;
+      if (cls == 0) continue;
+      const DeltaView::Row r = d.row(base + j * stride);
+      if (cls == 1) {
+        (void)d_mfp_run<true>(P, r.key, r.val, q.okeys + o * okw,
+                              q.ovals + o * ovb, lv, lt);
+        q.otimes[o] = r.t;
+        q.odiffs[o] = r.d;
+        o++;
+      } else {
+        q.ecodes[eo] = cls - 1;
+        q.etimes[eo] = r.t;
+        q.ediffs[eo] = r.d;
+        eo++;
+      }
+    }
+  }
+}
+
 // Smallest of the first *np times into *out (which starts at ~0): the
 // held buffer's next release time, read back with the push's closing copy.
 __global__ void k_time_min(const u64 *times, const u64 *np,
@@ -6481,6 +6711,131 @@ int mz_gpu_map(mz_gpu_ctx *c, const mz_gpu_schema *in,
                        flags, pos, pk, pv, pt, pd);
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   *out = make_out(pk, pv, pt, pd, M, okw, ovb);
+  return 0;
+}
+
+// ------------------------------------------------ scalar-expression MFP
+// Create-time validation of an expression program (mz_gpu.h lists what is
+// refused): the stack discipline by simulation, every COL inside the input
+// row, the OUT fields tiling the output row exactly. False with ctx->err
+// set when the program is refused.
+static bool mfp_validate(Ctx *ctx, const mz_gpu_mfp_spec *sp) {
+  auto fail = [&](const std::string &why) {
+    ctx->err = "mfp: " + why;
+    return false;
+  };
+  if (sp->n_ops > MZ_GPU_MAX_XOPS)
+    return fail("n_ops " + std::to_string(sp->n_ops) + " exceeds " +
+                std::to_string(MZ_GPU_MAX_XOPS));
+  if (is_varlen(sp->in.val_bytes) || is_varlen(sp->out.val_bytes))
+    return fail("varlen schemas unsupported");
+  for (const mz_gpu_schema *s : {&sp->in, &sp->out})
+    if (s->key_words < 1 || s->key_words > (u32)MAX_KW ||
+        s->val_bytes > (u32)MAX_VB)
+      return fail("schemas must have 1..2 key words and at most 64 val bytes");
+  u32 room[2] = {8 * sp->in.key_words, sp->in.val_bytes};
+  u32 oroom[2] = {8 * sp->out.key_words, sp->out.val_bytes};
+  u8 written[2][MAX_VB] = {};
+  u32 depth = 0;
+  for (u32 i = 0; i < sp->n_ops; i++) {
+    const mz_gpu_xop &op = sp->ops[i];
+    std::string at = "op " + std::to_string(i) + ": ";
+    u32 pops, pushes = 1;
+    switch (op.op) {
+      case MZ_X_COL:
+        if (op.src != MZ_SRC_KEY && op.src != MZ_SRC_VAL_STREAM)
+          return fail(at + "COL must read MZ_SRC_KEY or MZ_SRC_VAL_STREAM");
+        if (op.width != 1 && op.width != 4 && op.width != 8)
+          return fail(at + "COL width must be 1, 4 or 8");
+        if ((u32)op.off + op.width + (op.nullable ? 1 : 0) > room[op.src])
+          return fail(at + "COL reads past the input row's key or val");
+        pops = 0;
+        break;
+      case MZ_X_LIT:
+      case MZ_X_NULL: pops = 0; break;
+      case MZ_X_NEG:
+      case MZ_X_ABS:
+      case MZ_X_NOT:
+      case MZ_X_IS_NULL: pops = 1; break;
+      case MZ_X_IF: pops = 3; break;
+      case MZ_X_FILTER:
+      case MZ_X_OUT:
+        pops = 1;
+        pushes = 0;
+        break;
+      default:
+        if (op.op < MZ_X_ADD || op.op > MZ_X_COALESCE)
+          return fail(at + "unknown opcode " + std::to_string(op.op));
+        pops = 2;
+    }
+    if (depth < pops) return fail(at + "stack underflow");
+    depth = depth - pops + pushes;
+    if (depth > MZ_GPU_XSTACK)
+      return fail(at + "stack deeper than " + std::to_string(MZ_GPU_XSTACK));
+    if (!pushes && depth != 0)
+      return fail(at + "stack not empty after the statement");
+    if (op.op != MZ_X_OUT) continue;
+    if (op.src > 1) return fail(at + "OUT src must be 0 (key) or 1 (val)");
+    if (op.width != 1 && op.width != 4 && op.width != 8)
+      return fail(at + "OUT width must be 1, 4 or 8");
+    if (op.src == 0 && (op.width != 8 || op.nullable))
+      return fail(at + "a key OUT is 8 bytes wide and not nullable");
+    u32 end = (u32)op.off + op.width + (op.nullable ? 1 : 0);
+    if (end > oroom[op.src])
+      return fail(at + "OUT writes past the output row's key or val");
+    for (u32 b = op.off; b < end; b++) {
+      if (written[op.src][b]) return fail(at + "OUT fields overlap");
+      written[op.src][b] = 1;
+    }
+  }
+  if (depth != 0) return fail("stack not empty at the end of the program");
+  for (u32 s = 0; s < 2; s++)
+    for (u32 b = 0; b < oroom[s]; b++)
+      if (!written[s][b])
+        return fail(std::string("OUT fields leave a gap in the output ") +
+                    (s ? "val" : "key"));
+  return true;
+}
+
+// stage -> k_mfp_eval under the probe protocol's counters and timing
+// bracket (run_probe; the queues are exact, so its relaunch never fires)
+// -> consolidate (or hand back the raw queue) -> error stream.
+int mz_gpu_mfp(mz_gpu_ctx *c, const mz_gpu_mfp_spec *sp,
+               const mz_gpu_updates *u, int consolidate, mz_gpu_out **out) {
+  Ctx *ctx = &c->impl;
+  if (!mfp_validate(ctx, sp)) return 1;
+  (*ctx->scr).reset();
+  u32 kw = sp->in.key_words, vb = sp->in.val_bytes;
+  u32 okw = sp->out.key_words, ovb = sp->out.val_bytes;
+  DevUpdates d = stage_updates(ctx, u, kw, vb);
+  u64 n = d.n;
+  if (n == 0) {
+    *out = empty_out(ctx, okw, ovb);
+    return 0;
+  }
+  DeltaView dv{d.keys, d.vals, vb, d.times, d.diffs, n, kw};
+  ProbeQueue pq{okw, ovb};
+  ProbeCounts r = run_probe(ctx, pq, n, n, 2, n, [&](EmitQueue q) {
+    hipLaunchKernelGGL(k_mfp_eval, dim3(ngrid((n + MFP_ROWS - 1) / MFP_ROWS)),
+                       dim3(BLK), 0, ctx->stream, dv, *sp, q);
+  });
+  u64 M = r.M;
+  if (ctx->time_kernels)  // run_probe has synced and entered the call
+    ctx->probe_alg_bytes +=
+        n * (8ull * kw + vb + 16) + M * (8ull * okw + ovb + 16);
+  if (!consolidate) {
+    // raw rows in queue order; the consumer consolidates
+    *out = make_out(pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M, okw,
+                    ovb);
+  } else {
+    DevUpdates pin{pq.q.okeys, pq.q.ovals, pq.q.otimes, pq.q.odiffs, M};
+    u64 Mc;
+    FlatCols o = consolidate_dev(ctx, okw, ovb, pin, &Mc);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    pq.free_ok(ctx);
+    *out = make_out(o, Mc, okw, ovb);
+  }
+  attach_err_stream(ctx, *out, pq, r.E);
   return 0;
 }
 

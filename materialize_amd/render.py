@@ -654,6 +654,37 @@ def render_temporal_filter(ctx, plan: TemporalFilterPlan) -> TemporalFilterOp:
     return TemporalFilterOp(ctx, plan)
 
 
+@dataclass
+class MfpPlan:
+    """A MapFilterProject of scalar expressions (SafeMfpPlan,
+    src/expr/src/linear.rs) over one stream: `spec` from abi.mfp_spec.
+    consolidate=False hands the raw rows to a consolidating consumer (an
+    arrangement insert, a reduce)."""
+    spec: abi.MfpSpec
+    consolidate: bool = True
+
+
+class MfpOp:
+    """Stateless: each push maps its updates, row by row, at their own
+    times and diffs; rows whose evaluation errors are in the DevOut's error
+    stream."""
+
+    def __init__(self, ctx, plan: MfpPlan):
+        if not getattr(ctx, "supports_mfp", False):
+            raise NotImplementedError(
+                "this context does not implement scalar-expression MFPs")
+        self.ctx = ctx
+        self.plan = plan
+
+    def push(self, updates) -> DevOut:
+        return self.ctx.mfp_dev(self.plan.spec, updates,
+                                self.plan.consolidate)
+
+
+def render_mfp(ctx, plan: MfpPlan) -> MfpOp:
+    return MfpOp(ctx, plan)
+
+
 def render_delta_join(ctx, arrangements, plan, exchange=None) -> DeltaJoinOp:
     return DeltaJoinOp(ctx, arrangements, plan, exchange=exchange)
 
