@@ -730,6 +730,106 @@ int  mz_gpu_mfp(mz_gpu_ctx *ctx, const mz_gpu_mfp_spec *spec,
                 const mz_gpu_updates *updates, int consolidate,
                 mz_gpu_out **out);
 
+/* ------------------------------------------------------ window functions
+ * Replaces ReducePlan::Basic for the window AggregateFuncs — RowNumber,
+ * Rank, DenseRank, LagLead, FirstValue, LastValue
+ * (src/expr/src/relation/func.rs), which build_basic_aggregate
+ * (src/compute/src/render/reduce.rs) evaluates by recomputing a whole
+ * partition whenever any row of it changes and emitting new minus old. The
+ * operator owns an arrangement of the partition contents, as mz_gpu_topk
+ * does.
+ *
+ * Output row: the key unchanged; the val is the input val bytes followed by
+ * one slot per function, in spec order. A ROW_NUMBER, RANK or DENSE_RANK
+ * slot is an i64 (8 bytes). A value-function slot (LAG, LEAD, FIRST_VALUE,
+ * LAST_VALUE) is 9 bytes: the datum sign-extended to i64, then a null byte
+ * — what mz_gpu_mfp reads as `COL width 8 nullable`. NULL is eight zero
+ * bytes and null byte 1 (canonical, as mz_gpu_mfp's OUT). out.val_bytes =
+ * in.val_bytes + the slots, at most 64.
+ *
+ * Semantics. Take one partition (key) as of the push time: its rows
+ * (val, m), net multiplicity m > 0, ordered by the order columns, ties
+ * broken in the engine's canonical val order (the deviation TopK records,
+ * DESIGN.md §2.5). The reference repeats a row m times, so the partition is
+ * the expanded sequence E[0..M), M = sum of m, row r occupying [lo_r, hi_r).
+ * A peer group is a maximal run of rows whose order-column values are all
+ * equal; with n_order == 0 the whole partition is one peer group. At
+ * position p:
+ *   ROW_NUMBER   p + 1
+ *   RANK         lo of the first row of p's peer group, plus 1
+ *   DENSE_RANK   1 + the number of peer groups before p's
+ *   LAG(x, k)    the datum of E[p - k] if p - k >= 0, else the default
+ *   LEAD(x, k)   the datum of E[p + k] if p + k < M, else the default
+ *                (k = 0 is the row's own datum; a NULL datum stays NULL;
+ *                the default is `dflt` with has_default, else NULL)
+ *   FIRST_VALUE  the datum of E[0], for either frame
+ *   LAST_VALUE   MZ_WF_FRAME_TO_CURRENT: the datum of the last row of p's
+ *                peer group; MZ_WF_FRAME_PARTITION: the datum of E[M - 1]
+ * The partition's output is one row (key, val ++ slots) of diff 1 per
+ * position, consolidated. Each push returns corrections (reduce_abelian
+ * contract, as mz_gpu_topk): per changed partition -(old output) and
+ * +(new output) at the slice's time, consolidated and in canonical order,
+ * so unchanged rows cancel; a partition that becomes empty yields only
+ * retractions. Multi-timestamp pushes are processed per time slice, in time
+ * order.
+ *
+ * Expansion. The value differs between the copies of one row only for
+ * ROW_NUMBER, LAG and LEAD. A spec with none of them emits one output row
+ * per input row with diff m and never materialises M rows. A spec with one
+ * of them expands: a slice whose old or new expanded size exceeds 2^31 - 1
+ * fails the push with "window: expanded partition exceeds 2^31 rows" before
+ * anything of that size is allocated.
+ *
+ * Restrictions vs the reference: rows are emitted
+ * directly (no list + FlatMap unnest); literal LAG/LEAD offsets and
+ * defaults; RESPECT NULLS only; integer datums and order columns; the two
+ * frames above; no window aggregates (SUM(...) OVER), string_agg,
+ * array_agg.
+ *
+ * Refused at create (NULL, message in last_error): a varlen schema; a
+ * schema outside 1..2 key words; n_funcs outside 1..MZ_GPU_MAX_WFUNCS;
+ * n_order > MZ_GPU_MAX_ORDER; an order column or datum of width other than
+ * 4 or 8, or reading past in.val_bytes (the null byte included); an unknown
+ * func or frame; a nonzero frame on anything but LAST_VALUE; an `out` that
+ * is not the schema derived above. A snapshot with a negative net count
+ * fails the push with "negative multiplicities in window" (the reference's
+ * "Non-positive accumulation in ReduceInaccumulable"). After a failed push
+ * the operator may only be dropped. */
+enum { MZ_WF_ROW_NUMBER = 0, MZ_WF_RANK, MZ_WF_DENSE_RANK,
+       MZ_WF_LAG, MZ_WF_LEAD, MZ_WF_FIRST_VALUE, MZ_WF_LAST_VALUE };
+enum { MZ_WF_FRAME_TO_CURRENT = 0,   /* RANGE UNBOUNDED PRECEDING..CURRENT ROW
+                                        (SQL default; peers included)       */
+       MZ_WF_FRAME_PARTITION  = 1 }; /* UNBOUNDED PRECEDING..UNBOUNDED
+                                        FOLLOWING                           */
+typedef struct {            /* 24 bytes */
+  uint8_t  func;            /* MZ_WF_* */
+  uint8_t  width;           /* value functions: datum width 4 or 8, signed LE */
+  uint8_t  nullable;        /* value functions: null byte at off + width */
+  uint8_t  frame;           /* LAST_VALUE only; others must pass 0 */
+  uint16_t off;             /* value functions: datum offset in the input val */
+  uint8_t  has_default;     /* LAG/LEAD: 1 = `dflt` when out of partition,
+                               0 = NULL */
+  uint8_t  pad;
+  uint32_t offset;          /* LAG/LEAD: literal row offset >= 0 */
+  uint32_t pad2;
+  int64_t  dflt;
+} mz_gpu_window_func;
+#define MZ_GPU_MAX_WFUNCS 4
+typedef struct {
+  mz_gpu_schema in;         /* partition key words + row val bytes */
+  uint32_t n_order;         /* as TopK; 0 is legal */
+  mz_gpu_order_col order[MZ_GPU_MAX_ORDER];
+  uint32_t n_funcs;         /* 1..MZ_GPU_MAX_WFUNCS */
+  mz_gpu_window_func funcs[MZ_GPU_MAX_WFUNCS];
+  mz_gpu_schema out;        /* key_words = in.key_words; val = in val ++ slots */
+} mz_gpu_window_spec;
+typedef struct mz_gpu_window mz_gpu_window;
+mz_gpu_window *mz_gpu_window_create(mz_gpu_ctx *ctx,
+                                    const mz_gpu_window_spec *spec);
+int  mz_gpu_window_push(mz_gpu_ctx *ctx, mz_gpu_window *op,
+                        const mz_gpu_updates *delta, mz_gpu_out **out);
+void mz_gpu_window_drop(mz_gpu_ctx *ctx, mz_gpu_window *op);
+
 /* The routing hash itself (host helper; device code uses the same). */
 uint64_t mz_gpu_route_hash(const uint64_t *key_words, uint32_t n_words);
 

@@ -329,6 +329,157 @@ def topk_spec(in_schema, order, offset=0, limit=-1):
     return sp
 
 
+# ------------------------------------------------------ window functions
+# mz_gpu_window_*: ROW_NUMBER, RANK, DENSE_RANK, LAG / LEAD, FIRST_VALUE /
+# LAST_VALUE per partition (include/mz_gpu.h states the semantics).
+(MZ_WF_ROW_NUMBER, MZ_WF_RANK, MZ_WF_DENSE_RANK, MZ_WF_LAG, MZ_WF_LEAD,
+ MZ_WF_FIRST_VALUE, MZ_WF_LAST_VALUE) = range(7)
+MZ_WF_FRAME_TO_CURRENT, MZ_WF_FRAME_PARTITION = 0, 1
+MZ_GPU_MAX_WFUNCS = 4
+WF_RANK_SLOT_BYTES = 8    # ROW_NUMBER / RANK / DENSE_RANK: an i64
+WF_VALUE_SLOT_BYTES = 9   # value functions: i64 datum + null byte
+
+
+class WindowFunc(C.Structure):
+    """mz_gpu_window_func: one window function of a spec."""
+    _fields_ = [
+        ("func", C.c_uint8),
+        ("width", C.c_uint8),
+        ("nullable", C.c_uint8),
+        ("frame", C.c_uint8),
+        ("off", C.c_uint16),
+        ("has_default", C.c_uint8),
+        ("pad", C.c_uint8),
+        ("offset", C.c_uint32),
+        ("pad2", C.c_uint32),
+        ("dflt", C.c_int64),
+    ]
+
+
+class WindowSpec(C.Structure):
+    """mz_gpu_window_spec: partition schema, ORDER BY and the functions."""
+    _fields_ = [
+        ("in_", Schema),
+        ("n_order", C.c_uint32),
+        ("order", OrderCol * MZ_GPU_MAX_ORDER),
+        ("n_funcs", C.c_uint32),
+        ("funcs", WindowFunc * MZ_GPU_MAX_WFUNCS),
+        ("out", Schema),
+    ]
+
+
+def wf_is_value(func):
+    """LAG / LEAD / FIRST_VALUE / LAST_VALUE: the functions that read a
+    datum and fill a 9-byte slot."""
+    return func >= MZ_WF_LAG
+
+
+def wf_slot_bytes(func):
+    return WF_VALUE_SLOT_BYTES if wf_is_value(func) else WF_RANK_SLOT_BYTES
+
+
+def wf_row_number():
+    return WindowFunc(func=MZ_WF_ROW_NUMBER)
+
+
+def wf_rank():
+    return WindowFunc(func=MZ_WF_RANK)
+
+
+def wf_dense_rank():
+    return WindowFunc(func=MZ_WF_DENSE_RANK)
+
+
+def _wf_lag_lead(func, off, width, k, nullable, default):
+    if not 0 <= k < 2**32:
+        raise ValueError(f"window: LAG/LEAD offset {k} is not a u32")
+    if default is not None and not -2**63 <= default < 2**63:
+        raise ValueError(f"window: default {default} is not an i64")
+    return WindowFunc(func=func, off=off, width=width,
+                      nullable=1 if nullable else 0, offset=k,
+                      has_default=0 if default is None else 1,
+                      dflt=0 if default is None else default)
+
+
+def wf_lag(off, width, k=1, nullable=0, default=None):
+    """LAG(x, k, default) of the datum at `off`; default None = NULL."""
+    return _wf_lag_lead(MZ_WF_LAG, off, width, k, nullable, default)
+
+
+def wf_lead(off, width, k=1, nullable=0, default=None):
+    return _wf_lag_lead(MZ_WF_LEAD, off, width, k, nullable, default)
+
+
+def wf_first_value(off, width, nullable=0):
+    return WindowFunc(func=MZ_WF_FIRST_VALUE, off=off, width=width,
+                      nullable=1 if nullable else 0)
+
+
+def wf_last_value(off, width, nullable=0, frame=MZ_WF_FRAME_TO_CURRENT):
+    return WindowFunc(func=MZ_WF_LAST_VALUE, off=off, width=width,
+                      nullable=1 if nullable else 0, frame=frame)
+
+
+def window_spec(in_schema, order, funcs, out=None):
+    """mz_gpu_window_spec over rows of `in_schema`: `order` a list of
+    (off, width, desc) over the val bytes (may be empty), `funcs` 1..4 wf_*
+    items. Derives `out` (in val ++ one slot per function; a caller's `out`
+    must be that schema) and checks the operator's create-time rules here
+    as well as in the C layer (ValueError)."""
+    order, funcs = list(order), list(funcs)
+    kw, vb = in_schema.key_words, in_schema.val_bytes
+    if vb == MZ_GPU_VARLEN:
+        raise ValueError("window: varlen vals unsupported")
+    if not 1 <= kw <= MAX_KW:
+        raise ValueError("window: key_words must be 1 or 2")
+    if not 1 <= len(funcs) <= MZ_GPU_MAX_WFUNCS:
+        raise ValueError(f"window: n_funcs must be 1..{MZ_GPU_MAX_WFUNCS}, "
+                         f"got {len(funcs)}")
+    if len(order) > MZ_GPU_MAX_ORDER:
+        raise ValueError(f"window: n_order must be at most "
+                         f"{MZ_GPU_MAX_ORDER}, got {len(order)}")
+    for j, (off, width, _) in enumerate(order):
+        if width not in (4, 8):
+            raise ValueError(f"window: order column {j}: width must be 4 "
+                             "or 8")
+        if off + width > vb:
+            raise ValueError(f"window: order column {j} reads past "
+                             f"in.val_bytes ({vb})")
+    ovb = vb
+    for i, f in enumerate(funcs):
+        if f.func > MZ_WF_LAST_VALUE:
+            raise ValueError(f"window: func {i}: unknown func {f.func}")
+        if f.frame > MZ_WF_FRAME_PARTITION:
+            raise ValueError(f"window: func {i}: unknown frame {f.frame}")
+        if f.frame and f.func != MZ_WF_LAST_VALUE:
+            raise ValueError(f"window: func {i}: a frame is for LAST_VALUE "
+                             "only")
+        if wf_is_value(f.func):
+            if f.width not in (4, 8):
+                raise ValueError(f"window: func {i}: datum width must be 4 "
+                                 "or 8")
+            if f.off + f.width + (1 if f.nullable else 0) > vb:
+                raise ValueError(f"window: func {i} reads past in.val_bytes "
+                                 f"({vb})")
+        ovb += wf_slot_bytes(f.func)
+    if ovb > MAX_VB:
+        raise ValueError(f"window: out val is {ovb} bytes, more than "
+                         f"{MAX_VB}")
+    if out is not None and (out.key_words, out.val_bytes) != (kw, ovb):
+        raise ValueError(f"window: out schema must be {kw} key words and "
+                         f"{ovb} val bytes (in val ++ slots)")
+    sp = WindowSpec()
+    sp.in_ = in_schema
+    sp.n_order = len(order)
+    for j, (off, width, desc) in enumerate(order):
+        sp.order[j] = OrderCol(off=off, width=width, desc=1 if desc else 0)
+    sp.n_funcs = len(funcs)
+    for i, f in enumerate(funcs):
+        sp.funcs[i] = f
+    sp.out = Schema(key_words=kw, val_bytes=ovb)
+    return sp
+
+
 def is_distinct(agg):
     """COUNT/SUM(DISTINCT x). MIN/MAX carry the flag without effect: the
     extremum of a set is that of the multiset."""

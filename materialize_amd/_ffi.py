@@ -9,7 +9,8 @@ import os
 import subprocess
 
 from ._abi import (Closure, CollationSpec, MfpSpec, OutBatch, ReduceSpec,
-                   Schema, TemporalSpec, TopKSpec, Updates, out_to_numpy)
+                   Schema, TemporalSpec, TopKSpec, Updates, WindowSpec,
+                   out_to_numpy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "csrc", "libmzgpu.so")
@@ -159,6 +160,12 @@ def load():
     lib.mz_gpu_mfp.argtypes = [C.c_void_p, C.POINTER(MfpSpec),
                                C.POINTER(Updates), C.c_int,
                                C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_window_create.restype = C.c_void_p
+    lib.mz_gpu_window_create.argtypes = [C.c_void_p, C.POINTER(WindowSpec)]
+    lib.mz_gpu_window_push.argtypes = [C.c_void_p, C.c_void_p,
+                                       C.POINTER(Updates),
+                                       C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_window_drop.argtypes = [C.c_void_p, C.c_void_p]
     lib.mz_gpu_route_hash.restype = C.c_uint64
     lib.mz_gpu_route_hash.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
     lib.mz_gpu_set_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -185,6 +192,9 @@ class GpuCtx:
     # Scalar-expression MFPs (mz_gpu_mfp) are implemented here; render_mfp
     # refuses contexts that do not say so.
     supports_mfp = True
+    # Window functions (mz_gpu_window_*) are implemented here; render_window
+    # refuses contexts that do not say so.
+    supports_window = True
 
     def __init__(self, device=0):
         self.lib = load()
@@ -480,6 +490,28 @@ class GpuCtx:
         evaluation errors land in self.last_errs."""
         return self._take(self._mfp(spec, upd, consolidate))
 
+    def window_create(self, spec):
+        op = self.lib.mz_gpu_window_create(self.ctx, C.byref(spec))
+        if not op:
+            raise MzGpuError(self.lib.mz_gpu_last_error(self.ctx).decode())
+        return op
+
+    def _window_push(self, op, upd):
+        outp = C.POINTER(OutBatch)()
+        self._check(self.lib.mz_gpu_window_push(self.ctx, op, C.byref(upd),
+                                                C.byref(outp)))
+        return outp
+
+    def window_push(self, op, upd):
+        """Push a delta through a window-function operator: host columns of
+        the corrections (new minus old output rows of every changed
+        partition), consolidated and in canonical order. After a failed
+        push the operator may only be dropped."""
+        return self._take(self._window_push(op, upd))
+
+    def window_drop(self, op):
+        self.lib.mz_gpu_window_drop(self.ctx, op)
+
     # --- device-resident variants (outputs stay on the GPU; used by the
     # render layer to chain stages without host round trips) ---
     def _dev_out(self, outp, sorted=False):
@@ -523,6 +555,10 @@ class GpuCtx:
     def mfp_dev(self, spec, upd, consolidate=True):
         return self._dev_out(self._mfp(spec, upd, consolidate),
                              sorted=bool(consolidate))
+
+    def window_push_dev(self, op, upd):
+        # consolidated output in canonical order
+        return self._dev_out(self._window_push(op, upd), sorted=True)
 
     def halfjoin_dev(self, lookup, upd, stream_vb, le, cl):
         # raw (unconsolidated) output: the render layer's consumers —

@@ -2218,6 +2218,175 @@ __global__ void k_topk_kept(const u64 *keys, u32 kw, const u8 *vals, u32 vb,
   }
 }
 
+// ----------------------------------------------------- window functions
+// Per-row evaluation of RowNumber / Rank / DenseRank / LagLead /
+// FirstValue / LastValue (src/expr/src/relation/func.rs) over one ordered
+// snapshot — the TopK ordering: (key, order columns, canonical val).
+
+// d < 0 is the reference's "Non-positive accumulation" error (err[0]); a
+// single multiplicity beyond 2^31 - 1 already exceeds the expansion limit
+// (err[1]), and without one the u64 prefix sum cannot wrap.
+__global__ void k_window_check(const i64 *d, u64 n, u64 *err) {
+  GRID_STRIDE(i, n) {
+    if (d[i] < 0) err[0] = 1;
+    if (d[i] > 0x7FFFFFFFll) err[1] = 1;
+  }
+}
+
+struct WinOrder {
+  u32 n;
+  mz_gpu_order_col c[MZ_GPU_MAX_ORDER];
+};
+
+// Peer head flags of the ordered rows: the key or any order column differs
+// from the previous row (a partition head is a peer head). hidx = the row's
+// own index at a head, 0 elsewhere: its inclusive max-scan is each row's
+// peer-start index.
+__global__ void k_window_peer_flags(const u64 *keys, u32 kw, const u8 *vals,
+                                    u32 vb, WinOrder ord, u64 n, u32 *flags,
+                                    u32 *hidx) {
+  GRID_STRIDE(i, n) {
+    bool neq = i == 0;
+    for (u32 w = 0; w < kw && !neq; w++)
+      neq = keys[i * kw + w] != keys[(i - 1) * kw + w];
+    for (u32 j = 0; j < ord.n && !neq; j++) {
+      const u8 *a = vals + i * vb + ord.c[j].off;
+      neq = d_read_int(a, ord.c[j].width) != d_read_int(a - vb, ord.c[j].width);
+    }
+    flags[i] = neq ? 1u : 0u;
+    hidx[i] = neq ? (u32)i : 0u;
+  }
+}
+
+// first index in [lo, hi) whose value exceeds x (hi if none)
+template <typename T>
+__device__ __forceinline__ u64 d_upper_bound(const T *a, u64 lo, u64 hi, T x) {
+  while (lo < hi) {
+    u64 mid = (lo + hi) >> 1;
+    if (a[mid] > x)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  return lo;
+}
+
+// One ordered snapshot of n >= 1 rows: pre = inclusive scan of the diffs,
+// gid / starts = the partition groups, pstart = each row's peer-start row,
+// pcum = inclusive count of peer heads.
+struct WinSnap {
+  const u64 *keys;
+  const u8 *vals;
+  const u64 *pre;
+  const u32 *gid, *starts, *pstart, *pcum;
+  u64 n;
+};
+struct WinFuncs {
+  u32 n;
+  mz_gpu_window_func f[MZ_GPU_MAX_WFUNCS];
+};
+#define WIN_MAX_OVB 64
+
+// One thread per output row o of nout, written at row obase + o with
+// diff = sign * (expand ? 1 : the row's multiplicity). expand: o is a
+// position of the snapshot's expanded sequence and the source row comes
+// from an upper-bound search of pre; otherwise o is the row itself. Old
+// and new snapshots write disjoint ranges of one buffer: no atomics, and
+// the output position does not depend on scheduling. The val rows of a
+// block's tile are built in LDS and stored by the whole block, contiguous.
+__global__ void __launch_bounds__(BLK)
+k_window_emit(WinSnap s, WinFuncs F, u32 kw, u32 vb, u32 ovb, int expand,
+              u64 nout, u64 obase, u64 t, i64 sign, u64 *okeys, u8 *ovals,
+              u64 *otimes, i64 *odiffs) {
+  __shared__ u8 rows[BLK * WIN_MAX_OVB];
+  const u64 G = s.gid[s.n - 1];
+  for (u64 tile = (u64)blockIdx.x * BLK; tile < nout;
+       tile += (u64)gridDim.x * BLK) {
+    const u64 o = tile + threadIdx.x;
+    if (o < nout) {
+      u64 i = o;
+      if (expand) {
+        i = d_upper_bound<u64>(s.pre, 0, s.n, o);
+        if (i >= s.n) i = s.n - 1;
+      }
+      const u32 g = s.gid[i] - 1;
+      const u64 st = s.starts[g];
+      const u64 e = (u64)g + 1 < G ? (u64)s.starts[g + 1] : s.n;
+      const u64 base = st ? s.pre[st - 1] : 0;
+      const u64 M = s.pre[e - 1] - base;  // the partition's expanded size
+      const u64 p = o - base;             // position in it (expand only)
+      const u64 ps = s.pstart[i];
+      u8 *row = rows + threadIdx.x * ovb;
+      const u8 *v = s.vals + i * vb;
+      for (u32 b = 0; b < vb; b++) row[b] = v[b];
+      u32 w = vb;
+      for (u32 f = 0; f < F.n; f++) {
+        const mz_gpu_window_func fn = F.f[f];
+        u64 x = 0;
+        if (fn.func == MZ_WF_ROW_NUMBER) {
+          x = p + 1;
+        } else if (fn.func == MZ_WF_RANK) {
+          x = (ps == st ? 0 : s.pre[ps - 1] - base) + 1;
+        } else if (fn.func == MZ_WF_DENSE_RANK) {
+          x = (u64)(s.pcum[i] - s.pcum[st]) + 1;
+        } else {
+          u64 r = st;  // FIRST_VALUE
+          bool have = true;
+          if (fn.func == MZ_WF_LAG) {
+            have = p >= fn.offset;
+            r = have ? d_upper_bound<u64>(s.pre, st, e, base + p - fn.offset)
+                     : st;
+          } else if (fn.func == MZ_WF_LEAD) {
+            have = p + fn.offset < M;
+            r = have ? d_upper_bound<u64>(s.pre, st, e, base + p + fn.offset)
+                     : st;
+          } else if (fn.func == MZ_WF_LAST_VALUE) {
+            r = fn.frame == MZ_WF_FRAME_PARTITION
+                    ? e - 1
+                    : d_upper_bound<u32>(s.pstart, i + 1, e, (u32)ps) - 1;
+          }
+          if (r >= e) r = e - 1;
+          u8 nul;
+          if (have) {
+            const u8 *src = s.vals + r * vb + fn.off;
+            nul = fn.nullable && src[fn.width] != 0;
+            if (!nul) x = (u64)d_read_int(src, fn.width);
+          } else {
+            nul = !fn.has_default;
+            if (!nul) x = (u64)fn.dflt;
+          }
+          row[w + 8] = nul;
+        }
+        for (u32 b = 0; b < 8; b++) row[w + b] = (u8)(x >> (8 * b));
+        w += fn.func <= MZ_WF_DENSE_RANK ? 8 : 9;
+      }
+      for (u32 k = 0; k < kw; k++)
+        okeys[(obase + o) * kw + k] = s.keys[i * kw + k];
+      otimes[obase + o] = t;
+      const u64 m = s.pre[i] - (i ? s.pre[i - 1] : 0);
+      odiffs[obase + o] = expand ? sign : sign * (i64)m;
+    }
+    __syncthreads();
+    // the tile's rows are contiguous in the output: bytes up to the first
+    // 4-byte boundary, aligned words, then the tail
+    const u64 left = nout - tile;
+    const u32 nb = (u32)(left < BLK ? left : BLK) * ovb;
+    u8 *dst = ovals + (obase + tile) * ovb;
+    u32 head = (u32)((4 - ((uintptr_t)dst & 3)) & 3);
+    if (head > nb) head = nb;
+    const u32 nw = (nb - head) / 4;
+    for (u32 b = threadIdx.x; b < head; b += BLK) dst[b] = rows[b];
+    for (u32 q = threadIdx.x; q < nw; q += BLK) {
+      const u8 *sp = rows + head + 4 * q;
+      *(u32 *)(dst + head + 4 * q) = (u32)sp[0] | (u32)sp[1] << 8 |
+                                     (u32)sp[2] << 16 | (u32)sp[3] << 24;
+    }
+    for (u32 b = head + 4 * nw + threadIdx.x; b < nb; b += BLK)
+      dst[b] = rows[b];
+    __syncthreads();
+  }
+}
+
 __global__ void k_time_flags(const u64 *times, const u32 *perm, u32 *flags,
                              u64 n) {
   GRID_STRIDE(i, n)
@@ -2708,6 +2877,17 @@ struct mz_gpu_topk {
   mz_gpu_topk_spec spec;
   mz_gpu_arr *arr = nullptr;  // owned group-contents arrangement
   u64 *d_err = nullptr;
+};
+
+// Window-function operator (ReducePlan::Basic, build_basic_aggregate in
+// render/reduce.rs): TopK's shape — an owned arrangement of the partition
+// contents, changed partitions evaluated before and after each slice's
+// insert — with a per-row function evaluation and a wider output row.
+struct mz_gpu_window {
+  mz_gpu_window_spec spec;
+  mz_gpu_arr *arr = nullptr;  // owned partition-contents arrangement
+  u64 *d_err = nullptr;       // [0] negative count, [1] a count > 2^31 - 1
+  bool expand = false;        // ROW_NUMBER / LAG / LEAD: one row per copy
 };
 
 namespace {
@@ -6355,24 +6535,27 @@ static void topk_pass_cl(u32 kw, u32 vb, mz_gpu_closure &cl) {
   cl.out.val_bytes = vb;
 }
 
-// Order one eval set (a consolidated (key,val,net) snapshot of the
-// changed groups) by (group, order columns, canonical val tie-break),
-// compute each row's kept multiplicity window and append corrections
-// with the given sign. Stable LSD radix passes: order columns least-
-// significant first, then key words to regroup (compare_columns +
+// One eval set (a consolidated (key,val,net) snapshot of the changed
+// groups, pe->n >= 1 rows) ordered by (group, order columns, canonical val
+// tie-break), in scratch: the ordered columns, the key groups and the
+// inclusive scan of the diffs. Stable LSD radix passes: order columns
+// least-significant first, then key words to regroup (compare_columns +
 // Row-order tie-break restatement, top_k.rs:733-766).
-static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
-                           u64 t, i64 sign, u64 *pk, u8 *pv, u64 *pt,
-                           i64 *pd, unsigned long long *ocount) {
+struct OrderedSnap {
+  u64 *keys;
+  u8 *vals;
+  i64 *diffs;
+  Groups g;
+  u64 *pre;
+};
+static OrderedSnap order_snapshot(Ctx *ctx, u32 kw, u32 vb, u32 n_order,
+                                  const mz_gpu_order_col *order,
+                                  mz_gpu_out *pe) {
   u64 n = pe->n;
-  if (!n) return;
-  u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
   auto &S = (*ctx->scr);
   const u64 *keys = (const u64 *)pe->keys;
   const u8 *vals = (const u8 *)pe->vals;
   const i64 *diffs = (const i64 *)pe->diffs;
-  hipLaunchKernelGGL(k_check_pos, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     diffs, n, op->d_err);
   u32 *perm = (u32 *)S.get(n * 4);
   u32 *perm_out = (u32 *)S.get(n * 4);
   u64 *skey = (u64 *)S.get(n * 8);
@@ -6389,8 +6572,8 @@ static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
                                     (unsigned)n, 0, 64, ctx->stream);
     std::swap(perm, perm_out);
   };
-  for (int j = (int)op->spec.n_order - 1; j >= 0; j--) {
-    const mz_gpu_order_col &oc = op->spec.order[j];
+  for (int j = (int)n_order - 1; j >= 0; j--) {
+    const mz_gpu_order_col &oc = order[j];
     hipLaunchKernelGGL(k_order_sortkey, dim3(ngrid(n)), dim3(BLK), 0,
                        ctx->stream, vals, vb, perm, skey, n, (u32)oc.off,
                        (u32)oc.width, (u32)oc.desc);
@@ -6416,10 +6599,25 @@ static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
   Groups g = group_sorted(ctx, sk2, kw, (const u64 *)pe->times, n);
   u64 *pre = (u64 *)S.get(n * 8);
   inclusive_scan_u64(ctx, (const u64 *)sd2, pre, n);
+  return {sk2, sv2, sd2, g, pre};
+}
+
+// Order one eval set, compute each row's kept multiplicity window and
+// append corrections with the given sign.
+static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
+                           u64 t, i64 sign, u64 *pk, u8 *pv, u64 *pt,
+                           i64 *pd, unsigned long long *ocount) {
+  u64 n = pe->n;
+  if (!n) return;
+  u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
+  hipLaunchKernelGGL(k_check_pos, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
+                     (const i64 *)pe->diffs, n, op->d_err);
+  OrderedSnap s =
+      order_snapshot(ctx, kw, vb, op->spec.n_order, op->spec.order, pe);
   hipLaunchKernelGGL(k_topk_kept, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     sk2, kw, sv2, vb, sd2, pre, g.starts, g.gid, n,
-                     op->spec.offset, (i64)op->spec.limit, t, sign, pk, pv,
-                     pt, pd, ocount);
+                     s.keys, kw, s.vals, vb, s.diffs, s.pre, s.g.starts,
+                     s.g.gid, n, op->spec.offset, (i64)op->spec.limit, t,
+                     sign, pk, pv, pt, pd, ocount);
 }
 
 mz_gpu_topk *mz_gpu_topk_create(mz_gpu_ctx *c, const mz_gpu_topk_spec *spec) {
@@ -6579,6 +6777,285 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
   if (rc) return rc;
   if (errflag) {
     ctx->err = "negative multiplicities in TopK";
+    return -1;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------ window functions
+
+static inline bool wf_is_value(u8 func) { return func >= MZ_WF_LAG; }
+static inline u32 wf_slot_bytes(u8 func) { return wf_is_value(func) ? 9 : 8; }
+
+// The create-time rules of mz_gpu.h; "" when the spec is acceptable.
+static std::string window_spec_error(const mz_gpu_window_spec *sp) {
+  const u32 vb = sp->in.val_bytes;
+  if (is_varlen(vb) || is_varlen(sp->out.val_bytes))
+    return "varlen vals unsupported";
+  if (sp->in.key_words < 1 || sp->in.key_words > 2)
+    return "key_words must be 1 or 2";
+  if (sp->n_funcs < 1 || sp->n_funcs > MZ_GPU_MAX_WFUNCS)
+    return "n_funcs must be 1.." + std::to_string(MZ_GPU_MAX_WFUNCS);
+  if (sp->n_order > MZ_GPU_MAX_ORDER)
+    return "n_order must be at most " + std::to_string(MZ_GPU_MAX_ORDER);
+  for (u32 j = 0; j < sp->n_order; j++) {
+    const mz_gpu_order_col &oc = sp->order[j];
+    std::string who = "order column " + std::to_string(j);
+    if (oc.width != 4 && oc.width != 8) return who + ": width must be 4 or 8";
+    if ((u32)oc.off + oc.width > vb) return who + " reads past in.val_bytes";
+  }
+  u64 ovb = vb;
+  for (u32 f = 0; f < sp->n_funcs; f++) {
+    const mz_gpu_window_func &fn = sp->funcs[f];
+    std::string who = "func " + std::to_string(f);
+    if (fn.func > MZ_WF_LAST_VALUE)
+      return who + ": unknown func " + std::to_string(fn.func);
+    if (fn.frame > MZ_WF_FRAME_PARTITION)
+      return who + ": unknown frame " + std::to_string(fn.frame);
+    if (fn.frame && fn.func != MZ_WF_LAST_VALUE)
+      return who + ": a frame is for LAST_VALUE only";
+    if (wf_is_value(fn.func)) {
+      if (fn.width != 4 && fn.width != 8)
+        return who + ": datum width must be 4 or 8";
+      if ((u32)fn.off + fn.width + (fn.nullable ? 1u : 0u) > vb)
+        return who + " reads past in.val_bytes";
+    }
+    ovb += wf_slot_bytes(fn.func);
+  }
+  if (ovb > WIN_MAX_OVB)
+    return "out val is " + std::to_string(ovb) + " bytes, more than " +
+           std::to_string(WIN_MAX_OVB);
+  if (sp->out.key_words != sp->in.key_words || sp->out.val_bytes != ovb)
+    return "out schema must be in.key_words key words and " +
+           std::to_string(ovb) + " val bytes (in val ++ slots)";
+  return "";
+}
+
+mz_gpu_window *mz_gpu_window_create(mz_gpu_ctx *c,
+                                    const mz_gpu_window_spec *spec) {
+  Ctx *ctx = &c->impl;
+  std::string why = window_spec_error(spec);
+  if (!why.empty()) {
+    ctx->err = "window: " + why;
+    return nullptr;
+  }
+  mz_gpu_window *r = new mz_gpu_window();
+  r->spec = *spec;
+  for (u32 f = 0; f < spec->n_funcs; f++) {
+    u8 fn = spec->funcs[f].func;
+    r->expand |= fn == MZ_WF_ROW_NUMBER || fn == MZ_WF_LAG || fn == MZ_WF_LEAD;
+  }
+  r->arr = mz_gpu_arr_create(c, &spec->in);
+  r->d_err = dnew<u64>(ctx, 2);
+  fill_u64(ctx, r->d_err, 2, 0);
+  return r;
+}
+
+void mz_gpu_window_drop(mz_gpu_ctx *c, mz_gpu_window *op) {
+  mz_gpu_arr_drop(c, op->arr);  // owned partition-contents arrangement
+  dfree(&c->impl, op->d_err);
+  delete op;
+}
+
+// Order one eval set of pe->n >= 1 rows as TopK does and derive what the
+// emit kernel reads: peer head flags, their max-scan (peer-start rows) and
+// their sum-scan (dense ranks). All in scratch.
+static WinSnap window_eval(Ctx *ctx, mz_gpu_window *op, mz_gpu_out *pe) {
+  u64 n = pe->n;
+  u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
+  auto &S = (*ctx->scr);
+  hipLaunchKernelGGL(k_window_check, dim3(ngrid(n)), dim3(BLK), 0,
+                     ctx->stream, (const i64 *)pe->diffs, n, op->d_err);
+  OrderedSnap s =
+      order_snapshot(ctx, kw, vb, op->spec.n_order, op->spec.order, pe);
+  WinOrder ord;
+  ord.n = op->spec.n_order;
+  for (u32 j = 0; j < MZ_GPU_MAX_ORDER; j++) ord.c[j] = op->spec.order[j];
+  u32 *flags = (u32 *)S.get(n * 4);
+  u32 *hidx = (u32 *)S.get(n * 4);
+  hipLaunchKernelGGL(k_window_peer_flags, dim3(ngrid(n)), dim3(BLK), 0,
+                     ctx->stream, s.keys, kw, s.vals, vb, ord, n, flags,
+                     hidx);
+  u32 *pstart = (u32 *)S.get(n * 4);
+  size_t need = 0;
+  (void)rocprim::inclusive_scan(nullptr, need, hidx, pstart, n,
+                                rocprim::maximum<u32>(), ctx->stream);
+  void *tmp = S.get(need);
+  (void)rocprim::inclusive_scan(tmp, need, hidx, pstart, n,
+                                rocprim::maximum<u32>(), ctx->stream);
+  u32 *pcum = (u32 *)S.get(n * 4);
+  inclusive_scan_u32(ctx, flags, pcum, n);
+  return WinSnap{s.keys, s.vals, s.pre, s.g.gid, s.g.starts, pstart, pcum, n};
+}
+
+int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
+                       const mz_gpu_updates *u, mz_gpu_out **out) {
+  Ctx *ctx = &c->impl;
+  (*ctx->scr).reset();
+  const u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
+  const u32 ovb = op->spec.out.val_bytes;
+  const u64 kMaxExpanded = 0x7FFFFFFFull;
+  DevUpdates d = stage_updates(ctx, u, kw, vb);
+  u64 n = d.n;
+  if (n == 0) {
+    *out = empty_out(ctx, kw, ovb);
+    return 0;
+  }
+  // Owned sorted columns: they outlive spine merges' scratch resets.
+  u32 *perm = dnew<u32>(ctx, n);
+  sort_updates(ctx, d.keys, kw, d.vals, vb, d.times, n, perm, true);
+  u64 *sk = dnew<u64>(ctx, n * kw);
+  u8 *sv = (u8 *)dmalloc(ctx, std::max<u64>(n * vb, 1));
+  u64 *stm = dnew<u64>(ctx, n);
+  i64 *sd = dnew<i64>(ctx, n);
+  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
+                     ctx->stream, d.keys, kw, perm, sk, n);
+  if (vb)
+    hipLaunchKernelGGL(k_gather_valrows, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, d.vals, vb, perm, sv, n);
+  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
+                     d.times, perm, stm, n);
+  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
+                     d.diffs, perm, sd, n);
+  std::vector<TimeSlice> slices =
+      time_slices(ctx, stm, n, u->lower, u->upper);
+  WinFuncs F;
+  F.n = op->spec.n_funcs;
+  for (u32 f = 0; f < MZ_GPU_MAX_WFUNCS; f++) F.f[f] = op->spec.funcs[f];
+  std::vector<FlatCols> segs;
+  std::vector<u64> segn;
+  u64 total = 0;
+  int rc = 0;
+  bool negative = false, too_big = false;
+  for (auto [lo, hi, t] : slices) {
+    u64 m = hi - lo;
+    Groups g = group_sorted(ctx, sk + lo * kw, kw, stm + lo, m);
+    u64 G = *(u32 *)d2h_pinned(ctx, g.gid + (m - 1), 4);
+    u64 *dg = dnew<u64>(ctx, G * kw);
+    u64 *gt = dnew<u64>(ctx, G);
+    i64 *gd = dnew<i64>(ctx, G);
+    hipLaunchKernelGGL(k_gather_group_keys, dim3(ngrid(G)), dim3(BLK), 0,
+                       ctx->stream, sk + lo * kw, kw, g.starts, g.gid, m,
+                       dg);
+    fill_u64(ctx, gt, G, t);
+    fill_u64(ctx, (u64 *)gd, G, 1);
+    mz_gpu_updates su{};
+    su.keys = dg;
+    su.vals = nullptr;
+    su.times = gt;
+    su.diffs = gd;
+    su.n = G;
+    su.lower = t;
+    su.upper = t + 1;
+    su.on_device = 1;
+    mz_gpu_closure cl;
+    topk_pass_cl(kw, vb, cl);
+    // snapshot the changed partitions, install the slice, snapshot again
+    mz_gpu_out *oldp = nullptr, *newp = nullptr;
+    rc = probe_impl(ctx, op->arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &oldp);
+    if (!rc) {
+      DevUpdates sl{sk + lo * kw, vb ? sv + lo * vb : sv, stm + lo, sd + lo,
+                    m};
+      arr_insert_dev(ctx, op->arr, sl, t, t + 1);
+      rc = probe_impl(ctx, op->arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &newp);
+    }
+    if (!rc) {
+      WinSnap so{}, sn{};
+      if (oldp->n) so = window_eval(ctx, op, oldp);
+      if (newp->n) sn = window_eval(ctx, op, newp);
+      u64 mo = oldp->n, mn = newp->n;  // output rows of each snapshot
+      if (op->expand) {
+        // the expanded sizes are read back before anything of that size is
+        // allocated, with the error words that say whether they mean
+        // anything
+        u64 *stage = (u64 *)ctx->pin;
+        stage[0] = stage[1] = 0;
+        if (so.n)
+          HIP_CHECK(hipMemcpyAsync(stage, so.pre + (so.n - 1), 8,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        if (sn.n)
+          HIP_CHECK(hipMemcpyAsync(stage + 1, sn.pre + (sn.n - 1), 8,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(stage + 2, op->d_err, 16,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        mo = stage[0];
+        mn = stage[1];
+        negative = stage[2] != 0;
+        too_big = stage[3] != 0 || mo > kMaxExpanded || mn > kMaxExpanded;
+      }
+      if (!negative && !too_big && mo + mn) {
+        FlatCols seg = flat_alloc(ctx, mo + mn, kw, ovb);
+        if (mo)
+          hipLaunchKernelGGL(k_window_emit, dim3(ngrid(mo)), dim3(BLK), 0,
+                             ctx->stream, so, F, kw, vb, ovb,
+                             op->expand ? 1 : 0, mo, (u64)0, t, (i64)-1,
+                             seg.keys, seg.vals, seg.times, seg.diffs);
+        if (mn)
+          hipLaunchKernelGGL(k_window_emit, dim3(ngrid(mn)), dim3(BLK), 0,
+                             ctx->stream, sn, F, kw, vb, ovb,
+                             op->expand ? 1 : 0, mn, mo, t, (i64)1, seg.keys,
+                             seg.vals, seg.times, seg.diffs);
+        segs.push_back(seg);
+        segn.push_back(mo + mn);
+        total += mo + mn;
+      }
+    }
+    if (oldp) mz_gpu_out_release(c, oldp);
+    if (newp) mz_gpu_out_release(c, newp);
+    dfree(ctx, dg);
+    dfree(ctx, gt);
+    dfree(ctx, gd);
+    if (rc || negative || too_big) break;
+  }
+  if (!rc && !negative && !too_big && total > 0xFFFFFFFFull) too_big = true;
+  if (!rc && !negative && !too_big) {
+    if (total == 0) {
+      negative = *(u64 *)d2h_pinned(ctx, op->d_err, 8) != 0;
+      if (!negative) *out = empty_out(ctx, kw, ovb);
+    } else {
+      // one slice (the steady state) is consolidated where it was emitted
+      FlatCols all = segs[0];
+      if (segs.size() > 1) {
+        all = flat_alloc(ctx, total, kw, ovb);
+        u64 base = 0;
+        for (size_t i = 0; i < segs.size(); i++) {
+          u64 m2 = segn[i];
+          HIP_CHECK(hipMemcpyAsync(all.keys + base * kw, segs[i].keys,
+                                   m2 * kw * 8, hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+          HIP_CHECK(hipMemcpyAsync(all.vals + base * ovb, segs[i].vals,
+                                   m2 * ovb, hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+          HIP_CHECK(hipMemcpyAsync(all.times + base, segs[i].times, m2 * 8,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+          HIP_CHECK(hipMemcpyAsync(all.diffs + base, segs[i].diffs, m2 * 8,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+          base += m2;
+        }
+      }
+      DevUpdates pin{all.keys, all.vals, all.times, all.diffs, total};
+      u64 Mc;
+      FlatCols o = consolidate_dev(ctx, kw, ovb, pin, &Mc);
+      negative = *(u64 *)d2h_pinned(ctx, op->d_err, 8) != 0;
+      if (segs.size() > 1) flat_free(ctx, all);
+      if (negative)
+        flat_free(ctx, o);
+      else
+        *out = make_out(o, Mc, kw, ovb);
+    }
+  }
+  for (FlatCols &sg : segs) flat_free(ctx, sg);
+  for (void *p : {(void *)perm, (void *)sk, (void *)sv, (void *)stm,
+                  (void *)sd})
+    dfree(ctx, p);
+  if (rc) return rc;
+  if (negative) {
+    ctx->err = "negative multiplicities in window";
+    return -1;
+  }
+  if (too_big) {
+    ctx->err = "window: expanded partition exceeds 2^31 rows";
     return -1;
   }
   return 0;

@@ -685,6 +685,40 @@ def render_mfp(ctx, plan: MfpPlan) -> MfpOp:
     return MfpOp(ctx, plan)
 
 
+@dataclass
+class WindowPlan:
+    """Window functions over one partitioned, ordered input
+    (ReducePlan::Basic with AggregateFunc::RowNumber / Rank / DenseRank /
+    LagLead / FirstValue / LastValue): `spec` from abi.window_spec, its
+    functions from the abi.wf_* builders. Partition key = the input key."""
+    spec: abi.WindowSpec
+
+
+class WindowOp:
+    """build_basic_aggregate for window functions: each push re-evaluates
+    the changed partitions and returns new minus old output rows
+    (input val ++ one slot per function), consolidated."""
+
+    def __init__(self, ctx, plan: WindowPlan):
+        if not getattr(ctx, "supports_window", False):
+            raise NotImplementedError(
+                "this context does not implement window functions")
+        self.ctx = ctx
+        self.op = ctx.window_create(plan.spec)
+
+    def push(self, updates) -> DevOut:
+        return self.ctx.window_push_dev(self.op, updates)
+
+    def drop(self):
+        if self.op is not None:
+            self.ctx.window_drop(self.op)
+            self.op = None
+
+
+def render_window(ctx, plan: WindowPlan) -> WindowOp:
+    return WindowOp(ctx, plan)
+
+
 def render_delta_join(ctx, arrangements, plan, exchange=None) -> DeltaJoinOp:
     return DeltaJoinOp(ctx, arrangements, plan, exchange=exchange)
 
