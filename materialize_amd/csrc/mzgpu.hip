@@ -82,11 +82,54 @@ __global__ void k_gather_valrows(const u8 *src, u32 vb, const u32 *perm,
   }
 }
 
+// all four columns of an update stream at once (vb == 0: no val column)
+__global__ void k_gather_updates(const u64 *keys, u32 kw, const u8 *vals,
+                                 u32 vb, const u64 *times, const i64 *diffs,
+                                 const u32 *perm, u64 *okeys, u8 *ovals,
+                                 u64 *otimes, i64 *odiffs, u64 n) {
+  GRID_STRIDE(i, n) {
+    u64 r = perm[i];
+    for (u32 w = 0; w < kw; w++) okeys[i * kw + w] = keys[r * kw + w];
+    for (u32 b = 0; b < vb; b++) ovals[i * vb + b] = vals[r * vb + b];
+    otimes[i] = times[r];
+    odiffs[i] = diffs[r];
+  }
+}
+
+// Two update streams of n1 and n2 rows laid end to end, in one launch.
+__global__ void k_concat_updates(const u64 *k1, const u8 *v1, const u64 *t1,
+                                 const i64 *d1, u64 n1, const u64 *k2,
+                                 const u8 *v2, const u64 *t2, const i64 *d2,
+                                 u64 n2, u32 kw, u32 vb, u64 *okeys,
+                                 u8 *ovals, u64 *otimes, i64 *odiffs) {
+  GRID_STRIDE(i, n1 + n2) {
+    bool first = i < n1;
+    u64 r = first ? i : i - n1;
+    const u64 *k = first ? k1 : k2;
+    const u8 *v = first ? v1 : v2;
+    for (u32 w = 0; w < kw; w++) okeys[i * kw + w] = k[r * kw + w];
+    for (u32 b = 0; b < vb; b++) ovals[i * vb + b] = v[r * vb + b];
+    otimes[i] = (first ? t1 : t2)[r];
+    odiffs[i] = (first ? d1 : d2)[r];
+  }
+}
+
+// The sort-key kernels read row perm[i]. The first one of a sort has no
+// permutation yet: it gets `ident` instead, reads row i and writes the
+// identity there, which saves a separate iota launch.
+__device__ __forceinline__ u64 sort_row(const u32 *perm, u32 *ident, u64 i) {
+  if (!ident) return perm[i];
+  ident[i] = (u32)i;
+  return i;
+}
+
 // sort key for one key word: flip sign bit -> unsigned order == i64 order
 __global__ void k_sortkey_key(const u64 *keys, u32 kw, u32 word,
-                              const u32 *perm, u64 *out, u64 n, u64 sub) {
+                              const u32 *perm, u64 *out, u64 n, u64 sub,
+                              u32 *ident) {
   GRID_STRIDE(i, n)
-  out[i] = (keys[(u64)perm[i] * kw + word] ^ 0x8000000000000000ULL) - sub;
+  out[i] = (keys[sort_row(perm, ident, i) * kw + word] ^
+            0x8000000000000000ULL) - sub;
 }
 // sort key for one 8-byte val group: zero-padded little-endian u64 word
 // (the engine's canonical val order — matches oracle cmp_val)
@@ -101,9 +144,10 @@ __device__ __forceinline__ u64 le_val_word(const u8 *v, u32 rem) {
 }
 
 __global__ void k_sortkey_val(const u8 *vals, u32 vb, u32 word,
-                              const u32 *perm, u64 *out, u64 n, u64 sub) {
+                              const u32 *perm, u64 *out, u64 n, u64 sub,
+                              u32 *ident) {
   GRID_STRIDE(i, n) {
-    const u8 *v = vals + (u64)perm[i] * vb + word * 8;
+    const u8 *v = vals + sort_row(perm, ident, i) * vb + word * 8;
     out[i] = le_val_word(v, vb - word * 8) - sub;
   }
 }
@@ -163,8 +207,8 @@ __global__ void k_pass_minmax(const u64 *keys, u32 kw, const u8 *vals,
   }
 }
 __global__ void k_sortkey_u64(const u64 *src, const u32 *perm, u64 *out,
-                              u64 n, u64 sub) {
-  GRID_STRIDE(i, n) out[i] = src[perm[i]] - sub;
+                              u64 n, u64 sub, u32 *ident) {
+  GRID_STRIDE(i, n) out[i] = src[sort_row(perm, ident, i)] - sub;
 }
 
 // Composite radix key: several narrowed columns packed into one u64
@@ -181,9 +225,9 @@ struct CompSpec {
 
 __global__ void k_sortkey_comp(const u64 *keys, u32 kw, const u8 *vals,
                                u32 vb, const u64 *times, const u32 *perm,
-                               u64 *out, u64 n, CompSpec sp) {
+                               u64 *out, u64 n, CompSpec sp, u32 *ident) {
   GRID_STRIDE(i, n) {
-    u64 p = perm[i];
+    u64 p = sort_row(perm, ident, i);
     u64 acc = 0;
     for (u32 c = 0; c < sp.n; c++) {
       u64 x;
@@ -196,24 +240,6 @@ __global__ void k_sortkey_comp(const u64 *keys, u32 kw, const u8 *vals,
       acc |= (x - sp.sub[c]) << sp.shift[c];
     }
     out[i] = acc;
-  }
-}
-
-// head flags over the permuted (key,val,time) order
-__global__ void k_head_flags(const u64 *keys, u32 kw, const u8 *vals, u32 vb,
-                             const u64 *times, const u32 *perm, u32 *flags,
-                             u64 n, int with_time) {
-  GRID_STRIDE(i, n) {
-    if (i == 0) {
-      flags[0] = 1;
-      continue;
-    }
-    u64 a = perm[i], b = perm[i - 1];
-    bool neq = false;
-    for (u32 w = 0; w < kw; w++) neq |= keys[a * kw + w] != keys[b * kw + w];
-    for (u32 c = 0; c < vb && !neq; c++) neq |= vals[a * vb + c] != vals[b * vb + c];
-    if (with_time && !neq) neq = times[a] != times[b];
-    flags[i] = neq ? 1u : 0u;
   }
 }
 
@@ -242,23 +268,76 @@ __global__ void k_group_sums(const u32 *starts, const u32 *gid, u64 n,
   }
 }
 
-__global__ void k_emit_consolidated(const u64 *keys, u32 kw, const u8 *vals,
-                                    u32 vb, const u64 *times, const u32 *perm,
-                                    const u32 *starts, const i64 *gsum,
-                                    const u32 *nz, const u32 *nzpos,
-                                    const u32 *gid, u64 n, u64 *okeys,
-                                    u8 *ovals, u64 *otimes, i64 *odiffs,
-                                    u64 *dcounts /* [0] = M out */) {
-  u64 G = n ? gid[n - 1] : 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) dcounts[0] = nzpos[G];
-  GRID_STRIDE(g, G) {
-    if (!nz[g]) continue;
-    u64 o = nzpos[g];  // exclusive scan of nz
-    u64 r = perm[starts[g]];
+// ---- consolidation over a ready permutation: head flag +
+// permuted diff, one segmented scan, one survivor scan, one emit.
+
+// One scan element: the running wrapping diff sum of the row's group so
+// far, and whether a group starts at or before it within the scanned span.
+struct SegSum {
+  u64 sum;
+  u64 head;
+};
+// The segmented-sum operator (associative): a head on the right restarts.
+struct SegSumOp {
+  __host__ __device__ SegSum operator()(const SegSum &a,
+                                        const SegSum &b) const {
+    return b.head ? b : SegSum{a.sum + b.sum, a.head};
+  }
+};
+
+// head flag over the permuted (key,val,time) order, with the row's diff
+__global__ void k_head_diff(const u64 *keys, u32 kw, const u8 *vals, u32 vb,
+                            const u64 *times, const i64 *diffs,
+                            const u32 *perm, SegSum *hd, u64 n) {
+  GRID_STRIDE(i, n) {
+    u64 a = perm[i];
+    bool neq = i == 0;
+    if (!neq) {
+      u64 b = perm[i - 1];
+      for (u32 w = 0; w < kw; w++) neq |= keys[a * kw + w] != keys[b * kw + w];
+      for (u32 c = 0; c < vb && !neq; c++)
+        neq |= vals[a * vb + c] != vals[b * vb + c];
+      if (!neq) neq = times[a] != times[b];
+    }
+    hd[i] = SegSum{(u64)diffs[a], neq ? 1ull : 0ull};
+  }
+}
+
+// Row i survives iff it is the last of its group and the group's sum
+// (complete at its last row) is non-zero; 0 for the scan's padding slot.
+struct SurvivorIn {
+  const SegSum *hd, *seg;
+  u64 n;
+  __host__ __device__ u32 operator()(u64 i) const {
+    if (i >= n) return 0u;
+    bool last = i + 1 == n || hd[i + 1].head;
+    return last && seg[i].sum != 0 ? 1u : 0u;
+  }
+};
+
+// Each surviving group's last row writes the group's output row: all rows
+// of a group are equal on (key, val, time), so any of them serves. pos is
+// the exclusive scan of SurvivorIn over n + 1 slots, pos[n] the total.
+__global__ void k_emit_survivors(const u64 *keys, u32 kw, const u8 *vals,
+                                 u32 vb, const u64 *times, const u32 *perm,
+                                 SurvivorIn sv, const u32 *pos, u64 *okeys,
+                                 u8 *ovals, u64 *otimes, i64 *odiffs,
+                                 u64 *otimes2, i64 *odiffs2 /* or nullptr */,
+                                 u64 *dcounts /* [0] = M out */) {
+  u64 n = sv.n;
+  if (blockIdx.x == 0 && threadIdx.x == 0) dcounts[0] = pos[n];
+  GRID_STRIDE(i, n) {
+    if (!sv(i)) continue;
+    u64 o = pos[i];
+    u64 r = perm[i];
     for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = keys[r * kw + w];
     for (u32 c = 0; c < vb; c++) ovals[o * vb + c] = vals[r * vb + c];
     otimes[o] = times[r];
-    odiffs[o] = gsum[g];
+    odiffs[o] = (i64)sv.seg[i].sum;
+    if (otimes2) {
+      otimes2[o] = times[r];
+      odiffs2[o] = (i64)sv.seg[i].sum;
+    }
   }
 }
 
@@ -268,60 +347,57 @@ __global__ void k_advance_times(u64 *times, u64 n, u64 frontier) {
 
 // ----------------------------------------------- batch structure build
 
-// flags over SEALED (already sorted) arrays. The actual row count M is
-// read on-device from dcounts[0] (set by k_emit_consolidated); positions
-// beyond it get zero flags so capacity-sized scans stay exact.
-__global__ void k_change_flags(const u64 *keys, u32 kw, const u8 *vals,
-                               u32 vb, u32 *kc, u32 *vc, u64 cap,
-                               const u64 *dcounts) {
-  u64 n = dcounts ? dcounts[0] : cap;
-  GRID_STRIDE(i, cap) {
-    if (i >= n) {
-      kc[i] = 0;
-      vc[i] = 0;
-      continue;
-    }
-    if (i == 0) {
-      kc[0] = 1;
-      vc[0] = 1;
-      continue;
-    }
+// Change flags over SEALED (already sorted) arrays, as the input of ONE
+// scan: kc | vc << 32, where kc marks a row that opens a key and vc one that
+// opens a (key, val). Both totals stay below 2^32, so the packed u64 sum is
+// exact. The actual row count M is read on-device from dcounts[0] (set by
+// k_emit_survivors); positions beyond it count nothing, so the
+// capacity-sized scan stays exact.
+struct ChangeFlagsIn {
+  const u64 *keys;
+  const u8 *vals;
+  const u64 *dcounts;
+  u32 kw, vb;
+  __host__ __device__ u64 operator()(u64 i) const {
+    if (i >= dcounts[0]) return 0;
+    if (i == 0) return 1ull | 1ull << 32;
     bool kneq = false;
     for (u32 w = 0; w < kw; w++)
       kneq |= keys[i * kw + w] != keys[(i - 1) * kw + w];
     bool vneq = kneq;
     for (u32 c = 0; c < vb && !vneq; c++)
       vneq |= vals[i * vb + c] != vals[(i - 1) * vb + c];
-    kc[i] = kneq ? 1u : 0u;
-    vc[i] = vneq ? 1u : 0u;
+    return (kneq ? 1ull : 0ull) | (vneq ? 1ull << 32 : 0ull);
   }
-}
+};
 
+// ids: the inclusive scan of ChangeFlagsIn (key id low, val id high, both
+// 1-based); a row opens a key / a val where its id differs from the row
+// before.
 __global__ void k_scatter_structure(const u64 *keys, u32 kw, const u8 *vals,
-                                    u32 vb, const u32 *kc, const u32 *vc,
-                                    const u32 *kid /*inclusive*/,
-                                    const u32 *vid /*inclusive*/, u64 n,
+                                    u32 vb, const u64 *ids, u64 n,
                                     u64 *bkeys, u32 *kv_off, u8 *bvals,
                                     u32 *vu_off, u32 *val_key, u32 *upd_val,
                                     u64 *dcounts /* [0]=M in; [1]=nk,
                                                     [2]=nv out */) {
   u64 cap = n;
   n = dcounts[0];  // actual consolidated rows
-  u64 n_keys = n ? kid[cap - 1] : 0;  // zero flags beyond n keep this exact
-  u64 n_vals = n ? vid[cap - 1] : 0;
+  u64 n_keys = n ? (u32)ids[cap - 1] : 0;  // nothing counted beyond n
+  u64 n_vals = n ? ids[cap - 1] >> 32 : 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     dcounts[1] = n_keys;
     dcounts[2] = n_vals;
   }
   GRID_STRIDE(i, n) {
-    u32 k = kid[i] - 1, v = vid[i] - 1;
+    u64 id = ids[i], prev = i ? ids[i - 1] : 0;
+    u32 k = (u32)id - 1, v = (u32)(id >> 32) - 1;
     upd_val[i] = v;
-    if (kc[i]) {
+    if ((u32)id != (u32)prev) {
       for (u32 w = 0; w < kw; w++) bkeys[(u64)k * kw + w] = keys[i * kw + w];
       kv_off[k] = v;
       if (k == 0) kv_off[n_keys] = (u32)n_vals;
     }
-    if (vc[i]) {
+    if (id >> 32 != prev >> 32) {
       for (u32 c = 0; c < vb; c++) bvals[(u64)v * vb + c] = vals[i * vb + c];
       vu_off[v] = (u32)i;
       val_key[v] = k;
@@ -337,9 +413,9 @@ __global__ void k_scatter_structure(const u64 *keys, u32 kw, const u8 *vals,
 // kv_hi > kv_lo and n_vals < 2^32), so the CAS publishes the range
 // directly and no separate idx word is needed.
 __global__ void k_hash_build(u64 *hash, u64 slots, const u64 *keys, u32 kw,
-                             const u32 *kid, const u32 *kv_off, u64 cap,
-                             const u64 *dcounts) {
-  u64 n_keys = (cap && dcounts[0]) ? kid[cap - 1] : 0;
+                             const u32 *kv_off,
+                             const u64 *n_keys_p /* device word */) {
+  u64 n_keys = *n_keys_p;
   GRID_STRIDE(i, n_keys) {
     u64 h = route_hash(keys + i * kw, kw) & (slots - 1);
     u64 range = (u64)kv_off[i] | ((u64)kv_off[i + 1] << 32);
@@ -1781,39 +1857,98 @@ __device__ __forceinline__ bool acc_nonzero(const Acc5 &a) {
 }
 
 // A key whose old and new rows both exist and finalize to the same bytes
-// emits nothing.
-__device__ __forceinline__ void cancel_unchanged(bool &oe, bool &ne,
+// emits nothing. When they differ: whether the new row comes before the old
+// one in the canonical val order (le_val_word words, word 0 most
+// significant, unsigned, zero-padded tail). Read off the same byte sweep:
+// the first word that differs decides, and in it the highest byte.
+__device__ __forceinline__ bool cancel_unchanged(bool &oe, bool &ne,
                                                  const u8 *oldrow,
                                                  const u8 *newrow, u32 ovb) {
+  bool differ = false, new_first = false;
   if (oe && ne) {
-    bool same = true;
-    for (u32 c = 0; c < ovb; c++) same &= oldrow[c] == newrow[c];
-    if (same) oe = ne = false;
+    u32 word = 0;
+    for (u32 c = 0; c < ovb; c++) {
+      u8 a = oldrow[c], b = newrow[c];
+      if (a != b && (!differ || (c >> 3) == word)) {
+        differ = true;
+        word = c >> 3;
+        new_first = b < a;
+      }
+    }
+    if (!differ) oe = ne = false;
   }
+  return new_first;
 }
 
 // Emit the retraction of the old row and the assertion of the new one.
 // Every lane of the wave calls this once per iteration: ONE wave-aggregated
 // output reservation (per-row atomicAdds on the shared counter serialized
 // within each wave — same cure as the probe queues).
+//
+// Ordered form (gcount != nullptr; single-time pushes): no
+// reservation. Group g of the slice writes its 0, 1 or 2 rows to slots 2g
+// and 2g + 1 of the (staging) columns and their number to gcount[g]; of two
+// rows the one whose val comes first in the canonical val order goes first
+// (new_first, from cancel_unchanged).
+// Groups are in key order, so compacting the slots in group order
+// (k_compact_pairs) yields the consolidated form with no sort.
 __device__ __forceinline__ void emit_old_new(
     bool oe, bool ne, const u64 *key, u32 kw, const u8 *oldrow,
     const u8 *newrow, u32 ovb, u64 t, u32 lane, u64 *okeys, u8 *ovals,
-    u64 *otimes, i64 *odiffs, unsigned long long *ocount) {
+    u64 *otimes, i64 *odiffs, unsigned long long *ocount, u32 *gcount,
+    u64 g, bool live, bool new_first) {
   u32 c = (oe ? 1u : 0u) + (ne ? 1u : 0u);
-  u64 o = wave_reserve(ocount, c, lane);
+  u64 o;
+  if (gcount) {
+    if (!live) return;
+    gcount[g] = c;
+    o = 2 * g;
+  } else {
+    o = wave_reserve(ocount, c, lane);
+    new_first = false;  // the sort behind this form orders the rows
+  }
   if (oe) {
-    for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
-    for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = oldrow[cb];
-    otimes[o] = t;
-    odiffs[o] = -1;
-    o++;
+    u64 at = o + (new_first ? 1 : 0);
+    for (u32 w = 0; w < kw; w++) okeys[at * kw + w] = key[w];
+    for (u32 cb = 0; cb < ovb; cb++) ovals[at * ovb + cb] = oldrow[cb];
+    otimes[at] = t;
+    odiffs[at] = -1;
   }
   if (ne) {
-    for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = key[w];
-    for (u32 cb = 0; cb < ovb; cb++) ovals[o * ovb + cb] = newrow[cb];
-    otimes[o] = t;
-    odiffs[o] = 1;
+    u64 at = o + (oe && !new_first ? 1 : 0);
+    for (u32 w = 0; w < kw; w++) okeys[at * kw + w] = key[w];
+    for (u32 cb = 0; cb < ovb; cb++) ovals[at * ovb + cb] = newrow[cb];
+    otimes[at] = t;
+    odiffs[at] = 1;
+  }
+}
+
+// Compaction of the ordered emit: group g's gcount[g] rows move from slots
+// 2g.. to pos[g].., pos being the exclusive scan of PairCountIn over m + 1
+// slots; *ocount receives the total.
+struct PairCountIn {
+  const u32 *gcount, *gidn;
+  u64 m;
+  __host__ __device__ u32 operator()(u64 g) const {
+    return g < gidn[m - 1] ? gcount[g] : 0u;
+  }
+};
+__global__ void k_compact_pairs(const u64 *skeys, const u8 *svals,
+                                const u64 *stimes, const i64 *sdiffs,
+                                PairCountIn in, const u32 *pos, u32 kw,
+                                u32 vb, u64 *okeys, u8 *ovals, u64 *otimes,
+                                i64 *odiffs, unsigned long long *ocount) {
+  u64 G = in.gidn[in.m - 1];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ocount = pos[in.m];
+  GRID_STRIDE(g, G) {
+    u32 c = in.gcount[g];
+    for (u32 j = 0; j < c; j++) {
+      u64 s = 2 * g + j, o = (u64)pos[g] + j;
+      for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = skeys[s * kw + w];
+      for (u32 b = 0; b < vb; b++) ovals[o * vb + b] = svals[s * vb + b];
+      otimes[o] = stimes[s];
+      odiffs[o] = sdiffs[s];
+    }
   }
 }
 
@@ -1828,7 +1963,8 @@ __global__ void k_reduce_apply(const u64 *keys, const u8 *vals, u32 kw,
                                const u32 *miss, const u32 *misspos,
                                const u64 *d_nrows, mz_gpu_reduce_spec spec,
                                u64 *okeys, u8 *ovals, u64 *otimes,
-                               i64 *odiffs, unsigned long long *ocount) {
+                               i64 *odiffs, unsigned long long *ocount,
+                               u32 *gcount /* ordered emit, or nullptr */) {
   u32 na = spec.n_aggs;
   u32 ovb = spec.out.val_bytes;
   u64 G = hi_row ? gidn[hi_row - 1] : 0;
@@ -1839,7 +1975,7 @@ __global__ void k_reduce_apply(const u64 *keys, const u8 *vals, u32 kw,
   u32 lane = threadIdx.x & 63;
   for (u64 it = 0; it < iters; it++) {
     u64 g = start0 + it * stride;
-    bool oe = false, ne = false;
+    bool oe = false, ne = false, new_first = false;
     const u64 *key = nullptr;
     u8 oldrow[MZ_GPU_MAX_AGGS * 24], newrow[MZ_GPU_MAX_AGGS * 24];
     if (g < G) {
@@ -1877,11 +2013,11 @@ __global__ void k_reduce_apply(const u64 *keys, const u8 *vals, u32 kw,
         if (ne)
           for (u32 a = 0; a < na; a++)
             d_finalize(spec.aggs[a], accs[a], new_total, newrow + 24 * a);
-        cancel_unchanged(oe, ne, oldrow, newrow, ovb);
+        new_first = cancel_unchanged(oe, ne, oldrow, newrow, ovb);
       }
     }
     emit_old_new(oe, ne, key, kw, oldrow, newrow, ovb, t, lane, okeys, ovals,
-                 otimes, odiffs, ocount);
+                 otimes, odiffs, ocount, gcount, g, g < G, new_first);
   }
 }
 
@@ -2068,7 +2204,8 @@ k_reduce_apply_distinct(const u64 *keys, const u8 *vals, u32 kw, u32 vb,
                         const u32 *misspos, const u64 *d_nrows,
                         mz_gpu_reduce_spec spec, PairViews pvs, u64 *okeys,
                         u8 *ovals, u64 *otimes, i64 *odiffs,
-                        unsigned long long *ocount) {
+                        unsigned long long *ocount,
+                        u32 *gcount /* ordered emit, or nullptr */) {
   u32 na = spec.n_aggs;
   u32 ovb = spec.out.val_bytes;
   u32 kw2 = kw + 1;
@@ -2080,7 +2217,7 @@ k_reduce_apply_distinct(const u64 *keys, const u8 *vals, u32 kw, u32 vb,
   u32 lane = threadIdx.x & 63;
   for (u64 it = 0; it < iters; it++) {
     u64 g = start0 + it * stride;
-    bool oe = false, ne = false;
+    bool oe = false, ne = false, new_first = false;
     const u64 *key = nullptr;
     u8 oldrow[MZ_GPU_MAX_AGGS * 24], newrow[MZ_GPU_MAX_AGGS * 24];
     if (g < G) {
@@ -2134,11 +2271,11 @@ k_reduce_apply_distinct(const u64 *keys, const u8 *vals, u32 kw, u32 vb,
           d_finalize(ag, old_a, old_total, oldrow + 24 * a);
           d_finalize(ag, acc, new_total, newrow + 24 * a);
         }
-        cancel_unchanged(oe, ne, oldrow, newrow, ovb);
+        new_first = cancel_unchanged(oe, ne, oldrow, newrow, ovb);
       }
     }
     emit_old_new(oe, ne, key, kw, oldrow, newrow, ovb, t, lane, okeys, ovals,
-                 otimes, odiffs, ocount);
+                 otimes, odiffs, ocount, gcount, g, g < G, new_first);
   }
 }
 
@@ -2744,6 +2881,16 @@ struct Scratch {
 
 }  // namespace
 
+// Flat columns: four owned device arrays with room for n rows (at least
+// one), the form consolidation writes and build_batch_core / make_out
+// take over (DESIGN.md §4c).
+struct FlatCols {
+  u64 *keys = nullptr;
+  u8 *vals = nullptr;
+  u64 *times = nullptr;
+  i64 *diffs = nullptr;
+};
+
 struct DevUpdates {
   const u64 *keys;
   const u8 *vals;
@@ -2806,11 +2953,11 @@ struct mz_gpu_arr {
                     // upper <= lower cannot see this batch, so it need
                     // not force the flush (1-deep insert pipelining)
     u64 upper = 0;
-    // the insert's consolidated FLAT key/val rows (same order as
-    // batch.times/diffs), kept so mz_gpu_arr_flush_take can hand the
-    // sorted rows to the delta-path probes without re-sorting
-    u64 *flat_keys = nullptr;
-    u8 *flat_vals = nullptr;
+    // the insert's consolidated FLAT rows (same order and content as
+    // batch.times/diffs, in columns of their own), kept so
+    // mz_gpu_arr_flush_take can hand the sorted rows to the delta-path
+    // probes without re-sorting or copying
+    FlatCols flat;
   } pending;
   // deferred spine merge: the merged batch is computed on the lane while
   // probes keep using the pre-merge batch list (identical logical
@@ -3223,8 +3370,6 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
   u32 *perm_out = (u32 *)S.get(n * 4);
   void *tmp = nullptr;
   size_t tmp_bytes = 0;
-  hipLaunchKernelGGL(k_iota, dim3(ngrid(n)), dim3(BLK), 0, c->stream, perm,
-                     n);
   // Column min/max in one sweep: constant columns need no pass at all and
   // the rest subtract the min and radix-sort only the live bits (end_bit)
   // -- most benchmark columns are narrow (dates, keys, small decimals).
@@ -3339,7 +3484,18 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
     chunks.back().push_back(p);
     curbits += (u32)p.bits;
   }
-  size_t nchunks = 0;
+  // No chunk to sort (every column constant, or n == 0): the identity.
+  if (chunks.empty()) {
+    if (n)
+      hipLaunchKernelGGL(k_iota, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                         perm, n);
+    return;
+  }
+  // Each sort moves the permutation to the other buffer: start where the
+  // chunk count's parity makes the last one land in the caller's. The
+  // first sort-key kernel writes the identity there itself.
+  if (chunks.size() % 2 == 1) std::swap(perm, perm_out);
+  u32 *ident = perm;
   for (auto &ch : chunks) {
     int totbits = 0;
     if (ch.size() == 1) {
@@ -3347,15 +3503,15 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
       totbits = p.bits;
       if (p.kind == 0)
         hipLaunchKernelGGL(k_sortkey_u64, dim3(ngrid(n)), dim3(BLK), 0,
-                           c->stream, times, perm, skey, n, p.sub);
+                           c->stream, times, perm, skey, n, p.sub, ident);
       else if (p.kind == 1)
         hipLaunchKernelGGL(k_sortkey_val, dim3(ngrid(n)), dim3(BLK), 0,
                            c->stream, vals, vb, p.word, perm, skey, n,
-                           p.sub);
+                           p.sub, ident);
       else
         hipLaunchKernelGGL(k_sortkey_key, dim3(ngrid(n)), dim3(BLK), 0,
                            c->stream, keys, kw, p.word, perm, skey, n,
-                           p.sub);
+                           p.sub, ident);
     } else {
       CompSpec sp{};
       sp.n = (u32)ch.size();
@@ -3370,8 +3526,9 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
       totbits = (int)shift;
       hipLaunchKernelGGL(k_sortkey_comp, dim3(ngrid(n)), dim3(BLK), 0,
                          c->stream, keys, kw, vals, vb, times, perm, skey,
-                         n, sp);
+                         n, sp, ident);
     }
+    ident = nullptr;
     size_t need = 0;
     (void)rocprim::radix_sort_pairs(nullptr, need, skey, skey_out, perm,
                                     perm_out, (unsigned)n, 0, totbits,
@@ -3383,13 +3540,6 @@ void sort_updates(Ctx *c, const u64 *keys, u32 kw, const u8 *vals, u32 vb,
     (void)rocprim::radix_sort_pairs(tmp, tmp_bytes, skey, skey_out, perm,
                                     perm_out, (unsigned)n, 0, totbits,
                                     c->stream);
-    std::swap(perm, perm_out);
-    nchunks++;
-  }
-  // ensure the result lands in the caller's buffer
-  if (nchunks % 2 == 1) {
-    HIP_CHECK(hipMemcpyAsync(perm_out, perm, n * 4, hipMemcpyDeviceToDevice,
-                             c->stream));
     std::swap(perm, perm_out);
   }
 }
@@ -3548,15 +3698,6 @@ void out_attach_errs(mz_gpu_out *out, u64 *codes, u64 *times, i64 *diffs,
   out->err_diffs = diffs;
 }
 
-// Flat columns: four owned device arrays with room for n rows (at least
-// one), the form consolidation writes and build_batch_core / make_out
-// take over (DESIGN.md §4c).
-struct FlatCols {
-  u64 *keys = nullptr;
-  u8 *vals = nullptr;
-  u64 *times = nullptr;
-  i64 *diffs = nullptr;
-};
 FlatCols flat_alloc(Ctx *c, u64 n, u32 kw, u32 vb) {
   u64 capn = std::max<u64>(n, 1);
   FlatCols f;
@@ -3613,31 +3754,50 @@ GroupSums group_sum_by_perm(Ctx *c, const u32 *flags, const i64 *diffs,
 
 // Enqueue-only consolidation given a ready ordering permutation (group +
 // sum + compact) into CAPACITY-sized outputs (in.n rows); dcounts[0]
-// receives the consolidated row count on device.
+// receives the consolidated row count on device. times2/diffs2, when given,
+// receive a second copy of those two columns (the flush_take hand-off).
 void consolidate_with_perm(Ctx *c, u32 kw, u32 vb, DevUpdates in,
-                           const u32 *perm, const FlatCols &o,
-                           u64 *dcounts) {
+                           const u32 *perm, const FlatCols &o, u64 *dcounts,
+                           u64 *times2 = nullptr, i64 *diffs2 = nullptr) {
   auto &S = (*c->scr);
   u64 n = in.n;
   if (n == 0) {
     fill_u64(c, dcounts, 1, 0);
     return;
   }
-  u32 *flags = (u32 *)S.get(n * 4);
-  hipLaunchKernelGGL(k_head_flags, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     in.keys, kw, in.vals, vb, in.times, perm, flags, n, 1);
-  GroupSums g = group_sum_by_perm(c, flags, in.diffs, perm, n);
-  hipLaunchKernelGGL(k_emit_consolidated, dim3(ngrid(n)), dim3(BLK), 0,
-                     c->stream, in.keys, kw, in.vals, vb, in.times, perm,
-                     g.starts, g.gsum, g.nz, g.nzpos, g.gid, n, o.keys,
-                     o.vals, o.times, o.diffs, dcounts);
+  SegSum *hd = (SegSum *)S.get(n * sizeof(SegSum));
+  hipLaunchKernelGGL(k_head_diff, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
+                     in.keys, kw, in.vals, vb, in.times, in.diffs, perm, hd,
+                     n);
+  SegSum *seg = (SegSum *)S.get(n * sizeof(SegSum));
+  size_t need = 0;
+  (void)rocprim::inclusive_scan(nullptr, need, hd, seg, n, SegSumOp(),
+                                c->stream);
+  void *tmp = S.get(need);
+  (void)rocprim::inclusive_scan(tmp, need, hd, seg, n, SegSumOp(),
+                                c->stream);
+  SurvivorIn sv{hd, seg, n};
+  u32 *pos = (u32 *)S.get((n + 1) * 4);
+  auto it = rocprim::make_transform_iterator(
+      rocprim::make_counting_iterator<u64>(0), sv);
+  need = 0;
+  (void)rocprim::exclusive_scan(nullptr, need, it, pos, 0u, n + 1,
+                                rocprim::plus<u32>(), c->stream);
+  tmp = S.get(need);
+  (void)rocprim::exclusive_scan(tmp, need, it, pos, 0u, n + 1,
+                                rocprim::plus<u32>(), c->stream);
+  hipLaunchKernelGGL(k_emit_survivors, dim3(ngrid(n)), dim3(BLK), 0,
+                     c->stream, in.keys, kw, in.vals, vb, in.times, perm, sv,
+                     pos, o.keys, o.vals, o.times, o.diffs, times2, diffs2,
+                     dcounts);
 }
 
 // Core consolidation: sort + group + sum + compact, enqueue-only but for
 // the column-min/max read inside sort_updates (none with a cached plan).
 void consolidate_core(Ctx *c, u32 kw, u32 vb, DevUpdates in,
                       const FlatCols &o, u64 *dcounts,
-                      mz_gpu_arr::SortPlan *plan = nullptr) {
+                      mz_gpu_arr::SortPlan *plan = nullptr,
+                      u64 *times2 = nullptr, i64 *diffs2 = nullptr) {
   MZ_PROF(c, "consolidate_core");
   auto &S = (*c->scr);
   u64 n = in.n;
@@ -3648,7 +3808,7 @@ void consolidate_core(Ctx *c, u32 kw, u32 vb, DevUpdates in,
   u32 *perm = (u32 *)S.get(n * 4);
   sort_updates(c, in.keys, kw, in.vals, vb, in.times, n, perm, false,
                plan);
-  consolidate_with_perm(c, kw, vb, in, perm, o, dcounts);
+  consolidate_with_perm(c, kw, vb, in, perm, o, dcounts, times2, diffs2);
 }
 
 // Synchronous wrapper (ABI-level mz_gpu_consolidate and the consolidated
@@ -3766,15 +3926,9 @@ SortedCols sort_gather(Ctx *c, const u64 *keys, u32 kw, const u8 *vals,
   sort_updates(c, keys, kw, vals, vb, times, n, perm, true);
   SortedCols s{(u64 *)S.get(n * kw * 8), (u8 *)S.get(std::max<u64>(n * vb, 1)),
                (u64 *)S.get(n * 8), (i64 *)S.get(n * 8)};
-  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
-                     c->stream, keys, kw, perm, s.keys, n);
-  if (vb)
-    hipLaunchKernelGGL(k_gather_valrows, dim3(ngrid(n)), dim3(BLK), 0,
-                       c->stream, vals, vb, perm, s.vals, n);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     times, perm, s.times, n);
-  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, c->stream,
-                     diffs, perm, s.diffs, n);
+  hipLaunchKernelGGL(k_gather_updates, dim3(ngrid(n)), dim3(BLK), 0,
+                     c->stream, keys, kw, vals, vb, times, diffs, perm, s.keys,
+                     s.vals, s.times, s.diffs, n);
   return s;
 }
 
@@ -3875,14 +4029,18 @@ DevBatch build_batch_core(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals,
     }
     return b;
   }
-  u32 *kc = (u32 *)S.get(cap * 4);
-  u32 *vc = (u32 *)S.get(cap * 4);
-  hipLaunchKernelGGL(k_change_flags, dim3(ngrid(cap)), dim3(BLK), 0,
-                     c->stream, keys, kw, vals, vb, kc, vc, cap, dcounts);
-  u32 *kid = (u32 *)S.get(cap * 4);
-  u32 *vid = (u32 *)S.get(cap * 4);
-  inclusive_scan_u32(c, kc, kid, cap);
-  inclusive_scan_u32(c, vc, vid, cap);
+  u64 *ids = (u64 *)S.get(cap * 8);
+  {
+    auto it = rocprim::make_transform_iterator(
+        rocprim::make_counting_iterator<u64>(0),
+        ChangeFlagsIn{keys, vals, dcounts, kw, vb});
+    size_t need = 0;
+    (void)rocprim::inclusive_scan(nullptr, need, it, ids, cap,
+                                  rocprim::plus<u64>(), c->stream);
+    void *tmp = S.get(need);
+    (void)rocprim::inclusive_scan(tmp, need, it, ids, cap,
+                                  rocprim::plus<u64>(), c->stream);
+  }
   b.keys = dnew<u64>(c, cap * kw);
   b.kv_off = dnew<u32>(c, cap + 1);
   b.vals = (u8 *)dmalloc(c, std::max<u64>(cap * vb, 1));
@@ -3890,8 +4048,7 @@ DevBatch build_batch_core(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals,
   b.val_key = dnew<u32>(c, cap);
   b.upd_val = dnew<u32>(c, cap);
   hipLaunchKernelGGL(k_scatter_structure, dim3(ngrid(cap)), dim3(BLK), 0,
-                     c->stream, keys, kw, vals, vb, kc, vc, kid, vid, cap,
-                     b.keys, b.kv_off, b.vals, b.vu_off, b.val_key,
+                     c->stream, keys, kw, vals, vb, ids, cap, b.keys, b.kv_off, b.vals, b.vu_off, b.val_key,
                      b.upd_val, dcounts);
   b.times = times;
   b.diffs = diffs;
@@ -3903,8 +4060,8 @@ DevBatch build_batch_core(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals,
   // compares, so poisoned key words are never read
   fill_u64(c, b.hash, slots * (kw + 1), ~0ull);
   hipLaunchKernelGGL(k_hash_build, dim3(ngrid(cap)), dim3(BLK), 0,
-                     c->stream, b.hash, slots, b.keys, kw, kid, b.kv_off,
-                     cap, dcounts);
+                     c->stream, b.hash, slots, b.keys, kw, b.kv_off,
+                     dcounts + 1);
   // flat key/val arrays were re-packed; stream-ordered free is safe
   // (unless the caller keeps them for a flush_take hand-off)
   if (!keep_flat) {
@@ -3944,14 +4101,15 @@ DevBatch build_batch(Ctx *c, u32 kw, u32 vb, u64 *keys, u8 *vals, u64 *times,
 // the callers' guards choose it.
 
 // A sealed batch before its install: the batch with its host counts still
-// unset, the device words they will be read from (lane scratch), and the
-// flat key/val columns when the caller asked to keep them (times/diffs
-// always belong to the batch).
+// unset, the device words they will be read from (lane scratch), and, when
+// the caller asked to keep them, the consolidated flat rows as four columns
+// of their own: the flat keys and vals, and a copy of times and diffs that
+// the consolidation's emit wrote beside the batch's (which always belong to
+// the batch).
 struct Sealed {
   DevBatch batch;
   u64 *dcounts = nullptr;
-  u64 *flat_keys = nullptr;
-  u8 *flat_vals = nullptr;
+  FlatCols flat;
 };
 
 // The seal's tail, enqueue-only: consolidate `in` along a ready ordering
@@ -3965,16 +4123,18 @@ Sealed seal_ordered(Ctx *c, u32 kw, u32 vb, DevUpdates in, const u32 *perm,
   FlatCols o = flat_alloc(c, in.n, kw, vb);
   Sealed s;
   s.dcounts = (u64 *)(*c->scr).get(3 * 8);
+  if (keep_flat) {  // sized by capacity: the count is still on the device
+    u64 capn = std::max<u64>(in.n, 1);
+    s.flat = FlatCols{o.keys, o.vals, dnew<u64>(c, capn), dnew<i64>(c, capn)};
+  }
   if (perm)
-    consolidate_with_perm(c, kw, vb, in, perm, o, s.dcounts);
+    consolidate_with_perm(c, kw, vb, in, perm, o, s.dcounts, s.flat.times,
+                          s.flat.diffs);
   else
-    consolidate_core(c, kw, vb, in, o, s.dcounts, plan);
+    consolidate_core(c, kw, vb, in, o, s.dcounts, plan, s.flat.times,
+                     s.flat.diffs);
   s.batch = build_batch_core(c, kw, vb, o.keys, o.vals, o.times, o.diffs,
                              in.n, lower, upper, s.dcounts, keep_flat);
-  if (keep_flat) {
-    s.flat_keys = o.keys;
-    s.flat_vals = o.vals;
-  }
   return s;
 }
 
@@ -4493,19 +4653,15 @@ DevBatch build_batch_vl(Ctx *c, u32 kw, VlCols &&in, u64 lower, u64 upper) {
   b.hash_slots = slots;
   b.hash = dnew<u64>(c, slots * (kw + 1));
   fill_u64(c, b.hash, slots * (kw + 1), ~0ull);
-  // reuse the fixed-width hash build: it reads keys/kid/kv_off only.
-  // kid for distinct keys = identity over n_keys; pass a counting setup:
+  // reuse the fixed-width hash build: it reads keys/kv_off and the key
+  // count from a device word
   {
-    u32 *kid2 = (u32 *)S.get(std::max<u64>(n_keys, 1) * 4);
-    hipLaunchKernelGGL(k_iota_off, dim3(ngrid(std::max<u64>(n_keys, 1))),
-                       dim3(BLK), 0, c->stream, kid2,
-                       std::max<u64>(n_keys, 1), 1);
     u64 *dc = (u64 *)S.get(8);
     hipLaunchKernelGGL(k_write_u64, dim3(1), dim3(1), 0, c->stream, dc,
                        n_keys);
     hipLaunchKernelGGL(k_hash_build, dim3(ngrid(std::max<u64>(n_keys, 1))),
                        dim3(BLK), 0, c->stream, b.hash, slots, b.keys, kw,
-                       kid2, b.kv_off, n_keys, dc);
+                       b.kv_off, dc);
   }
   for (void *p : {(void *)in.keys, (void *)in.voffs, (void *)in.arena})
     dfree(c, p);
@@ -5023,8 +5179,7 @@ static void arr_release_lanes(mz_gpu_arr *a) {
 static void arr_release_state(Ctx *ctx, mz_gpu_arr *a) {
   for (auto &b : a->batches) free_batch(ctx, b);
   a->batches.clear();
-  dfree(ctx, a->pending.flat_keys);
-  dfree(ctx, a->pending.flat_vals);
+  flat_free(ctx, a->pending.flat);
   dfree(ctx, a->sort_plan.dev);
   dfree(ctx, a->sort_plan.d_flag);
   if (a->pending.active) free_batch(ctx, a->pending.batch);
@@ -5303,8 +5458,7 @@ static void insert_pipeline(Ctx *ctx, mz_gpu_arr *a, DevUpdates d,
   a->pending.staged = d;
   a->pending.lower = lower;
   a->pending.upper = upper;
-  a->pending.flat_keys = s.flat_keys;
-  a->pending.flat_vals = s.flat_vals;
+  a->pending.flat = s.flat;
   a->pending.flag[0] = 0;
   HIP_CHECK(hipMemcpyAsync(a->pending.cnt, s.dcounts, 3 * 8,
                            hipMemcpyDeviceToHost, ctx->stream));
@@ -5355,8 +5509,7 @@ static void arr_flush_take_impl(Ctx *ctx, mz_gpu_arr *a,
     // the cached sort plan did not cover this batch: discard the
     // mis-sorted build and redo synchronously (re-priming the cache)
     free_batch(ctx, a->pending.batch);
-    dfree(ctx, a->pending.flat_keys);
-    dfree(ctx, a->pending.flat_vals);
+    flat_free(ctx, a->pending.flat);
     a->sort_plan.valid = 0;
     (*ctx->scr).reset();  // redo inputs are device-resident, not staged
     insert_pipeline(ctx, a, a->pending.staged, a->pending.lower,
@@ -5376,27 +5529,15 @@ static void arr_flush_take_impl(Ctx *ctx, mz_gpu_arr *a,
     a->pending.active = 0;
     u32 kw = a->schema.kw, vb = a->schema.vb;
     if (take && b.n_upds) {
-      // hand the consolidated flat rows over as a sorted out-batch:
-      // keys/vals transfer ownership; times/diffs are copied (the batch
-      // owns its columns and a spine merge may free them)
-      u64 *tc = dnew<u64>(ctx, b.n_upds);
-      i64 *dc = dnew<i64>(ctx, b.n_upds);
-      HIP_CHECK(hipMemcpyAsync(tc, b.times, b.n_upds * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-      HIP_CHECK(hipMemcpyAsync(dc, b.diffs, b.n_upds * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-      *take = make_out(a->pending.flat_keys, a->pending.flat_vals, tc, dc,
-                       b.n_upds, kw, vb);
-      a->pending.flat_keys = nullptr;
-      a->pending.flat_vals = nullptr;
-      // the out's consumers run on other streams; its columns must be
-      // complete before the flush returns
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      // hand the consolidated flat rows over as a sorted out-batch that
+      // owns its four columns (the batch owns its own times/diffs, which
+      // a spine merge may free). The lane wrote them all before the
+      // synchronisation above, so the out's consumers, which run on
+      // other streams, find them complete.
+      *take = make_out(a->pending.flat, b.n_upds, kw, vb);
+      a->pending.flat = FlatCols();
     } else {
-      dfree(ctx, a->pending.flat_keys);
-      dfree(ctx, a->pending.flat_vals);
-      a->pending.flat_keys = nullptr;
-      a->pending.flat_vals = nullptr;
+      flat_free(ctx, a->pending.flat);
     }
   }
   // Synchronous merges by default: deferral was re-measured (round 2)
@@ -6345,19 +6486,11 @@ int mz_gpu_reduce_push2(mz_gpu_ctx *c, mz_gpu_red *op,
   u8 *v = (u8 *)S.get(std::max<u64>(capn * vb, 1));
   u64 *t = (u64 *)S.get(capn * 8);
   i64 *df = (i64 *)S.get(capn * 8);
-  auto cat = [&](void *dst, const void *a, u64 abytes, const void *b,
-                 u64 bbytes) {
-    if (abytes)
-      HIP_CHECK(hipMemcpyAsync(dst, a, abytes, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-    if (bbytes)
-      HIP_CHECK(hipMemcpyAsync((char *)dst + abytes, b, bbytes,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-  };
-  cat(k, d1.keys, d1.n * kw * 8, d2.keys, d2.n * kw * 8);
-  if (vb) cat(v, d1.vals, d1.n * vb, d2.vals, d2.n * vb);
-  cat(t, d1.times, d1.n * 8, d2.times, d2.n * 8);
-  cat(df, d1.diffs, d1.n * 8, d2.diffs, d2.n * 8);
+  if (n)
+    hipLaunchKernelGGL(k_concat_updates, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, d1.keys, d1.vals, d1.times, d1.diffs,
+                       d1.n, d2.keys, d2.vals, d2.times, d2.diffs, d2.n, kw,
+                       vb, k, v, t, df);
   DevUpdates d{k, v, t, df, n};
   return reduce_push_dev_impl(ctx, op, d,
                               std::min(u1->lower, u2->lower),
@@ -6382,6 +6515,20 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
   // capacity 2 * n corrections max (each input row can change at most one
   // key per slice; 2 rows per changed key per slice)
   CorrBuf cb = corr_alloc(ctx, 2 * n + 16, okw, ovb);
+  // A single-time push emits in canonical order (emit_old_new's ordered
+  // form): two staging slots per group, compacted into cb after the apply.
+  // Across several times the canonical order is key-major, so those pushes
+  // keep the reservation and corr_finish's sort.
+  bool ordered = upper == lower + 1;
+  CorrBuf em = cb;  // where the apply kernel writes
+  u32 *gcount = nullptr;
+  if (ordered) {
+    em.pk = (u64 *)S.get(2 * n * okw * 8);
+    em.pv = (u8 *)S.get(std::max<u64>(2 * n * ovb, 1));
+    em.pt = (u64 *)S.get(2 * n * 8);
+    em.pd = (i64 *)S.get(2 * n * 8);
+    gcount = (u32 *)S.get(n * 4);
+  }
   // DISTINCT aggregates: the (key, datum) stream of each, sorted by
   // (time, key, datum). NULL datums stay as neutral rows, so the sorted
   // times equal s.times and the slices below cut both streams alike.
@@ -6430,22 +6577,46 @@ static int reduce_push_dev_impl(Ctx *ctx, mz_gpu_red *op, DevUpdates d,
                          0, ctx->stream, sk, s.vals + lo * vb, kw, vb,
                          s.diffs + lo, g.starts, g.gid, m, t, op->tbl.st,
                          up.found, up.miss, up.misspos, op->tbl.d_nrows,
-                         op->spec, pvs, cb.pk, cb.pv, cb.pt, cb.pd,
-                         cb.ocount);
+                         op->spec, pvs, em.pk, em.pv, em.pt, em.pd,
+                         em.ocount, gcount);
     else
       hipLaunchKernelGGL(k_reduce_apply, dim3(ngrid(m)), dim3(BLK), 0,
                          ctx->stream, sk, s.vals + lo * vb, kw, vb,
                          s.diffs + lo, g.starts, g.gid, m, t, op->tbl.st,
                          up.found, up.miss, up.misspos, op->tbl.d_nrows,
-                         op->spec, cb.pk, cb.pv, cb.pt, cb.pd, cb.ocount);
+                         op->spec, em.pk, em.pv, em.pt, em.pd, em.ocount,
+                         gcount);
     kt_commit(ctx, op->tbl, up, g, m);
+    if (ordered) {  // the one slice: m == n
+      PairCountIn pc{gcount, g.gid, m};
+      u32 *pos = (u32 *)S.get((m + 1) * 4);
+      auto it = rocprim::make_transform_iterator(
+          rocprim::make_counting_iterator<u64>(0), pc);
+      size_t need = 0;
+      (void)rocprim::exclusive_scan(nullptr, need, it, pos, 0u, m + 1,
+                                    rocprim::plus<u32>(), ctx->stream);
+      void *tmp = S.get(need);
+      (void)rocprim::exclusive_scan(tmp, need, it, pos, 0u, m + 1,
+                                    rocprim::plus<u32>(), ctx->stream);
+      hipLaunchKernelGGL(k_compact_pairs, dim3(ngrid(m)), dim3(BLK), 0,
+                         ctx->stream, em.pk, em.pv, em.pt, em.pd, pc, pos, okw,
+                         ovb, cb.pk, cb.pv, cb.pt, cb.pd, cb.ocount);
+    }
   }
   // count + the whole counter block [key rows][err][pair rows] at once
   const u64 *h = corr_read(ctx, cb, op->d_ctr, 2 + op->n_dist);
   u64 emitted = h[0], errflag = h[2];
   op->tbl.n_rows = h[1];
   for (u32 j = 0; j < op->n_dist; j++) op->ptbl[j].n_rows = h[3 + j];
-  mz_gpu_out *o = corr_finish(ctx, cb, emitted, errflag != 0);
+  mz_gpu_out *o;
+  if (!ordered) {
+    o = corr_finish(ctx, cb, emitted, errflag != 0);
+  } else if (errflag) {
+    corr_free(ctx, cb);
+    o = nullptr;
+  } else {  // already consolidated: cb's columns become the result
+    o = make_out(cb.pk, cb.pv, cb.pt, cb.pd, emitted, okw, ovb);
+  }
   if (errflag) {
     ctx->err = "reduce state capacity exceeded";
     return -1;
@@ -6582,7 +6753,7 @@ static OrderedSnap order_snapshot(Ctx *ctx, u32 kw, u32 vb, u32 n_order,
   for (int w = (int)kw - 1; w >= 0; w--) {
     hipLaunchKernelGGL(k_sortkey_key, dim3(ngrid(n)), dim3(BLK), 0,
                        ctx->stream, keys, kw, (u32)w, perm, skey, n,
-                       (u64)0);
+                       (u64)0, (u32 *)nullptr);
     radix_pass();
   }
   u64 *sk2 = (u64 *)S.get(n * kw * 8);
