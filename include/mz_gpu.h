@@ -732,18 +732,19 @@ int  mz_gpu_mfp(mz_gpu_ctx *ctx, const mz_gpu_mfp_spec *spec,
 
 /* ------------------------------------------------------ window functions
  * Replaces ReducePlan::Basic for the window AggregateFuncs — RowNumber,
- * Rank, DenseRank, LagLead, FirstValue, LastValue
- * (src/expr/src/relation/func.rs), which build_basic_aggregate
- * (src/compute/src/render/reduce.rs) evaluates by recomputing a whole
+ * Rank, DenseRank, LagLead, FirstValue, LastValue and WindowAggregate over
+ * SUM / COUNT / MIN / MAX (src/expr/src/relation/func.rs), which
+ * build_basic_aggregate (src/compute/src/render/reduce.rs) evaluates by
+ * recomputing a whole
  * partition whenever any row of it changes and emitting new minus old. The
  * operator owns an arrangement of the partition contents, as mz_gpu_topk
  * does.
  *
  * Output row: the key unchanged; the val is the input val bytes followed by
- * one slot per function, in spec order. A ROW_NUMBER, RANK or DENSE_RANK
- * slot is an i64 (8 bytes). A value-function slot (LAG, LEAD, FIRST_VALUE,
- * LAST_VALUE) is 9 bytes: the datum sign-extended to i64, then a null byte
- * — what mz_gpu_mfp reads as `COL width 8 nullable`. NULL is eight zero
+ * one slot per function, in spec order. A ROW_NUMBER, RANK, DENSE_RANK or
+ * COUNT slot is an i64 (8 bytes). A value slot (LAG, LEAD, FIRST_VALUE,
+ * LAST_VALUE, SUM, MIN, MAX) is 9 bytes: the datum sign-extended to i64,
+ * then a null byte — what mz_gpu_mfp reads as `COL width 8 nullable`. NULL is eight zero
  * bytes and null byte 1 (canonical, as mz_gpu_mfp's OUT). out.val_bytes =
  * in.val_bytes + the slots, at most 64.
  *
@@ -774,44 +775,97 @@ int  mz_gpu_mfp(mz_gpu_ctx *ctx, const mz_gpu_mfp_spec *spec,
  * order.
  *
  * Expansion. The value differs between the copies of one row only for
- * ROW_NUMBER, LAG and LEAD. A spec with none of them emits one output row
- * per input row with diff m and never materialises M rows. A spec with one
+ * ROW_NUMBER, LAG, LEAD and the ROWS aggregates below. A spec with none of
+ * them emits one output row per input row with diff m and never
+ * materialises M rows. A spec with one
  * of them expands: a slice whose old or new expanded size exceeds 2^31 - 1
  * fails the push with "window: expanded partition exceeds 2^31 rows" before
  * anything of that size is allocated.
  *
+ * Window aggregates: SUM, COUNT, MIN, MAX over a frame of E. For these
+ * `off` / `width` / `nullable` describe the datum as for the value
+ * functions; COUNT with width == 0 is COUNT(*), COUNT with a datum counts
+ * its non-NULLs. The frame of position p:
+ *   MZ_WF_FRAME_TO_CURRENT  E[0 .. last position of p's peer group] (RANGE
+ *                           UNBOUNDED PRECEDING..CURRENT ROW, the SQL
+ *                           default; peers included)
+ *   MZ_WF_FRAME_PARTITION   E[0 .. M - 1]
+ *   MZ_WF_FRAME_ROWS        E[a .. b], a = 0 | p - k | p | p + k by the start
+ *                           bound, b = p - k' | p | p + k' | M - 1 by the end
+ *                           bound, clipped to [0, M - 1]; empty if a > b.
+ *                           `bounds` = start kind | end kind << 4 (MZ_WB_*),
+ *                           `offset` = k, `end_offset` = k'. `bounds` and
+ *                           `end_offset` are the bytes other functions leave
+ *                           zero as `pad` and `pad2`.
+ * Over the frame's non-NULL datums (all of them for COUNT(*)):
+ *   SUM    NULL if there are none, else their exact sum
+ *   COUNT  their number; 0 for an empty frame
+ *   MIN    NULL if there are none, else the least
+ *   MAX    NULL if there are none, else the greatest
+ * COUNT fills an i64 slot (8 bytes) like the ranks; SUM, MIN and MAX fill
+ * the 9-byte value slot, so AVG is SUM / COUNT in a downstream mz_gpu_mfp.
+ * SUM accumulates exactly in 128 bits; a frame sum outside int64 fails the
+ * push with "window: SUM out of int64 range" (the reference widens
+ * sum(int8) to numeric). A spec holding SUM bounds every
+ * multiplicity by 2^31 - 1 whether or not it expands: a larger one fails the
+ * push with the expansion message below. A ROWS aggregate distinguishes the
+ * copies of a row and expands, except with both ends unbounded, which is
+ * the whole partition; TO_CURRENT and PARTITION aggregates do not expand.
+ *
  * Restrictions vs the reference: rows are emitted
- * directly (no list + FlatMap unnest); literal LAG/LEAD offsets and
- * defaults; RESPECT NULLS only; integer datums and order columns; the two
- * frames above; no window aggregates (SUM(...) OVER), string_agg,
- * array_agg.
+ * directly (no list + FlatMap unnest); literal LAG/LEAD offsets, defaults
+ * and frame bounds; RESPECT NULLS only; integer datums and order columns.
+ * Not provided: GROUPS frames; RANGE frames with offsets; MIN / MAX over a
+ * ROWS frame bounded on both sides (it needs a range-minimum structure);
+ * AVG (compose SUM and COUNT with mz_gpu_mfp); string_agg, array_agg.
  *
  * Refused at create (NULL, message in last_error): a varlen schema; a
  * schema outside 1..2 key words; n_funcs outside 1..MZ_GPU_MAX_WFUNCS;
  * n_order > MZ_GPU_MAX_ORDER; an order column or datum of width other than
- * 4 or 8, or reading past in.val_bytes (the null byte included); an unknown
- * func or frame; a nonzero frame on anything but LAST_VALUE; an `out` that
- * is not the schema derived above. A snapshot with a negative net count
- * fails the push with "negative multiplicities in window" (the reference's
- * "Non-positive accumulation in ReduceInaccumulable"). After a failed push
- * the operator may only be dropped. */
+ * 4 or 8 (COUNT(*)'s 0 excepted), or reading past in.val_bytes (the null
+ * byte included); an unknown func or frame; a nonzero frame on anything but
+ * LAST_VALUE and the aggregates; MZ_WF_FRAME_ROWS on anything but the
+ * aggregates; for an aggregate: an unknown bound kind, a start of UNBOUNDED
+ * FOLLOWING, an end of UNBOUNDED PRECEDING, a start of CURRENT ROW with an
+ * end of PRECEDING, a start of FOLLOWING with an end of PRECEDING or
+ * CURRENT ROW (k PRECEDING .. k' PRECEDING is legal for any k, k' and may
+ * be empty), a nonzero offset on an UNBOUNDED or CURRENT ROW bound, nonzero
+ * bounds or offsets without MZ_WF_FRAME_ROWS, COUNT(*) with off or
+ * nullable set, has_default or dflt set, MIN / MAX with a ROWS frame of which neither end
+ * is UNBOUNDED; an `out` that is not the schema derived above. A snapshot
+ * with a negative net count fails the push with "negative multiplicities in
+ * window" (the reference's "Non-positive accumulation in
+ * ReduceInaccumulable"). After a failed push the operator may only be
+ * dropped. */
 enum { MZ_WF_ROW_NUMBER = 0, MZ_WF_RANK, MZ_WF_DENSE_RANK,
-       MZ_WF_LAG, MZ_WF_LEAD, MZ_WF_FIRST_VALUE, MZ_WF_LAST_VALUE };
+       MZ_WF_LAG, MZ_WF_LEAD, MZ_WF_FIRST_VALUE, MZ_WF_LAST_VALUE,
+       /* 7..15 are unknown */
+       MZ_WF_SUM = 16, MZ_WF_COUNT = 17, MZ_WF_MIN = 18, MZ_WF_MAX = 19 };
 enum { MZ_WF_FRAME_TO_CURRENT = 0,   /* RANGE UNBOUNDED PRECEDING..CURRENT ROW
                                         (SQL default; peers included)       */
-       MZ_WF_FRAME_PARTITION  = 1 }; /* UNBOUNDED PRECEDING..UNBOUNDED
+       MZ_WF_FRAME_PARTITION  = 1,   /* UNBOUNDED PRECEDING..UNBOUNDED
                                         FOLLOWING                           */
+       MZ_WF_FRAME_ROWS       = 2 }; /* ROWS start..end; aggregates only   */
+enum { MZ_WB_UNBOUNDED_PRECEDING = 0, MZ_WB_PRECEDING, MZ_WB_CURRENT_ROW,
+       MZ_WB_FOLLOWING, MZ_WB_UNBOUNDED_FOLLOWING };
 typedef struct {            /* 24 bytes */
   uint8_t  func;            /* MZ_WF_* */
-  uint8_t  width;           /* value functions: datum width 4 or 8, signed LE */
-  uint8_t  nullable;        /* value functions: null byte at off + width */
-  uint8_t  frame;           /* LAST_VALUE only; others must pass 0 */
-  uint16_t off;             /* value functions: datum offset in the input val */
+  uint8_t  width;           /* datum width 4 or 8, signed LE; COUNT(*): 0 */
+  uint8_t  nullable;        /* null byte at off + width */
+  uint8_t  frame;           /* LAST_VALUE and aggregates; others pass 0 */
+  uint16_t off;             /* datum offset in the input val */
   uint8_t  has_default;     /* LAG/LEAD: 1 = `dflt` when out of partition,
                                0 = NULL */
-  uint8_t  pad;
-  uint32_t offset;          /* LAG/LEAD: literal row offset >= 0 */
-  uint32_t pad2;
+  union {
+    uint8_t pad;
+    uint8_t bounds;         /* ROWS aggregates: start kind | end kind << 4 */
+  };
+  uint32_t offset;          /* LAG/LEAD: literal row offset >= 0; ROWS
+                               aggregates: the start bound's k */
+  union {
+    uint32_t pad2;
+    uint32_t end_offset;    /* ROWS aggregates: the end bound's k' */
+  };
   int64_t  dflt;
 } mz_gpu_window_func;
 #define MZ_GPU_MAX_WFUNCS 4

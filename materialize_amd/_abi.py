@@ -331,17 +331,31 @@ def topk_spec(in_schema, order, offset=0, limit=-1):
 
 # ------------------------------------------------------ window functions
 # mz_gpu_window_*: ROW_NUMBER, RANK, DENSE_RANK, LAG / LEAD, FIRST_VALUE /
-# LAST_VALUE per partition (include/mz_gpu.h states the semantics).
+# LAST_VALUE and the aggregates SUM / COUNT / MIN / MAX over a frame, per
+# partition (include/mz_gpu.h states the semantics).
 (MZ_WF_ROW_NUMBER, MZ_WF_RANK, MZ_WF_DENSE_RANK, MZ_WF_LAG, MZ_WF_LEAD,
  MZ_WF_FIRST_VALUE, MZ_WF_LAST_VALUE) = range(7)
-MZ_WF_FRAME_TO_CURRENT, MZ_WF_FRAME_PARTITION = 0, 1
+MZ_WF_SUM, MZ_WF_COUNT, MZ_WF_MIN, MZ_WF_MAX = 16, 17, 18, 19  # 7..15 unknown
+MZ_WF_FRAME_TO_CURRENT, MZ_WF_FRAME_PARTITION, MZ_WF_FRAME_ROWS = 0, 1, 2
+(MZ_WB_UNBOUNDED_PRECEDING, MZ_WB_PRECEDING, MZ_WB_CURRENT_ROW,
+ MZ_WB_FOLLOWING, MZ_WB_UNBOUNDED_FOLLOWING) = range(5)
 MZ_GPU_MAX_WFUNCS = 4
-WF_RANK_SLOT_BYTES = 8    # ROW_NUMBER / RANK / DENSE_RANK: an i64
-WF_VALUE_SLOT_BYTES = 9   # value functions: i64 datum + null byte
+WF_RANK_SLOT_BYTES = 8    # ROW_NUMBER / RANK / DENSE_RANK / COUNT: an i64
+WF_VALUE_SLOT_BYTES = 9   # value functions, SUM / MIN / MAX: i64 + null byte
+
+
+class _WindowFuncBounds(C.Union):
+    _fields_ = [("pad", C.c_uint8), ("bounds", C.c_uint8)]
+
+
+class _WindowFuncEnd(C.Union):
+    _fields_ = [("pad2", C.c_uint32), ("end_offset", C.c_uint32)]
 
 
 class WindowFunc(C.Structure):
-    """mz_gpu_window_func: one window function of a spec."""
+    """mz_gpu_window_func: one window function of a spec. `bounds` and
+    `end_offset` (ROWS aggregates) are second names of `pad` and `pad2`."""
+    _anonymous_ = ("_bounds", "_end")
     _fields_ = [
         ("func", C.c_uint8),
         ("width", C.c_uint8),
@@ -349,9 +363,9 @@ class WindowFunc(C.Structure):
         ("frame", C.c_uint8),
         ("off", C.c_uint16),
         ("has_default", C.c_uint8),
-        ("pad", C.c_uint8),
+        ("_bounds", _WindowFuncBounds),
         ("offset", C.c_uint32),
-        ("pad2", C.c_uint32),
+        ("_end", _WindowFuncEnd),
         ("dflt", C.c_int64),
     ]
 
@@ -368,14 +382,28 @@ class WindowSpec(C.Structure):
     ]
 
 
+def wf_is_agg(func):
+    return MZ_WF_SUM <= func <= MZ_WF_MAX
+
+
 def wf_is_value(func):
-    """LAG / LEAD / FIRST_VALUE / LAST_VALUE: the functions that read a
-    datum and fill a 9-byte slot."""
-    return func >= MZ_WF_LAG
+    """LAG / LEAD / FIRST_VALUE / LAST_VALUE / SUM / MIN / MAX: the
+    functions that fill a 9-byte value slot. COUNT fills an i64."""
+    return func >= MZ_WF_LAG and func != MZ_WF_COUNT
 
 
 def wf_slot_bytes(func):
     return WF_VALUE_SLOT_BYTES if wf_is_value(func) else WF_RANK_SLOT_BYTES
+
+
+def wf_expands(f):
+    """Does the function's value differ between the copies of one row? The
+    ranking by position, LAG / LEAD, and a ROWS aggregate unless both ends
+    are unbounded (the whole partition)."""
+    if wf_is_agg(f.func):
+        return f.frame == MZ_WF_FRAME_ROWS and f.bounds != (
+            MZ_WB_UNBOUNDED_PRECEDING | MZ_WB_UNBOUNDED_FOLLOWING << 4)
+    return f.func in (MZ_WF_ROW_NUMBER, MZ_WF_LAG, MZ_WF_LEAD)
 
 
 def wf_row_number():
@@ -420,6 +448,112 @@ def wf_last_value(off, width, nullable=0, frame=MZ_WF_FRAME_TO_CURRENT):
                       nullable=1 if nullable else 0, frame=frame)
 
 
+UNBOUNDED_PRECEDING = (MZ_WB_UNBOUNDED_PRECEDING, 0)
+CURRENT_ROW = (MZ_WB_CURRENT_ROW, 0)
+UNBOUNDED_FOLLOWING = (MZ_WB_UNBOUNDED_FOLLOWING, 0)
+
+
+def preceding(k):
+    return (MZ_WB_PRECEDING, k)
+
+
+def following(k):
+    return (MZ_WB_FOLLOWING, k)
+
+
+def _wf_agg(func, off, width, nullable, frame, start, end):
+    """One aggregate. `start` / `end` are (MZ_WB_* kind, k) pairs — the
+    names above — and either of them selects MZ_WF_FRAME_ROWS; with neither,
+    `frame` (default: the SQL default, MZ_WF_FRAME_TO_CURRENT) stands."""
+    f = WindowFunc(func=func, off=off, width=width,
+                   nullable=1 if nullable else 0)
+    if start is None and end is None:
+        f.frame = MZ_WF_FRAME_TO_CURRENT if frame is None else frame
+        return f
+    if frame not in (None, MZ_WF_FRAME_ROWS):
+        raise ValueError("window: start / end bounds need MZ_WF_FRAME_ROWS")
+    (sk, k), (ek, k2) = (start or UNBOUNDED_PRECEDING), (end or CURRENT_ROW)
+    for kind, n in ((sk, k), (ek, k2)):
+        if not 0 <= kind < 16:
+            raise ValueError(f"window: bound kind {kind} is not a nibble")
+        if not 0 <= n < 2**32:
+            raise ValueError(f"window: frame offset {n} is not a u32")
+    f.frame = MZ_WF_FRAME_ROWS
+    f.bounds = sk | ek << 4
+    f.offset, f.end_offset = k, k2
+    return f
+
+
+def wf_sum(off, width, nullable=0, frame=None, start=None, end=None):
+    """SUM(x) OVER the frame, of the datum at `off`. abi.wf_sum(8, 8,
+    start=abi.preceding(2), end=abi.CURRENT_ROW) is ROWS BETWEEN 2 PRECEDING
+    AND CURRENT ROW; a missing start is UNBOUNDED PRECEDING, a missing end
+    CURRENT ROW."""
+    return _wf_agg(MZ_WF_SUM, off, width, nullable, frame, start, end)
+
+
+def wf_count(off=0, width=0, nullable=0, frame=None, start=None, end=None):
+    """COUNT(x) OVER the frame; width 0 (the default) is COUNT(*)."""
+    return _wf_agg(MZ_WF_COUNT, off, width, nullable, frame, start, end)
+
+
+def wf_min(off, width, nullable=0, frame=None, start=None, end=None):
+    return _wf_agg(MZ_WF_MIN, off, width, nullable, frame, start, end)
+
+
+def wf_max(off, width, nullable=0, frame=None, start=None, end=None):
+    return _wf_agg(MZ_WF_MAX, off, width, nullable, frame, start, end)
+
+
+def _window_agg_check(who, f, vb):
+    """An aggregate's create-time rules, as window_agg_error in
+    csrc/window_spec.h."""
+    if f.frame > MZ_WF_FRAME_ROWS:
+        raise ValueError(f"{who}: unknown frame {f.frame}")
+    star = f.func == MZ_WF_COUNT and f.width == 0
+    if not star and f.width not in (4, 8):
+        raise ValueError(f"{who}: datum width must be 4 or 8"
+                         + (", or 0 for COUNT(*)" if f.func == MZ_WF_COUNT
+                            else ""))
+    if star and (f.off or f.nullable):
+        raise ValueError(f"{who}: COUNT(*) takes no datum")
+    if not star and f.off + f.width + (1 if f.nullable else 0) > vb:
+        raise ValueError(f"{who} reads past in.val_bytes ({vb})")
+    if f.has_default or f.dflt:
+        raise ValueError(f"{who}: an aggregate takes no default")
+    if f.frame != MZ_WF_FRAME_ROWS:
+        if f.bounds or f.offset or f.end_offset:
+            raise ValueError(f"{who}: bounds and offsets need "
+                             "MZ_WF_FRAME_ROWS")
+        return
+    sk, ek = f.bounds & 15, f.bounds >> 4
+    PREC, FOLL = MZ_WB_PRECEDING, MZ_WB_FOLLOWING
+    for kind in (sk, ek):
+        if kind > MZ_WB_UNBOUNDED_FOLLOWING:
+            raise ValueError(f"{who}: unknown bound kind {kind}")
+    if sk == MZ_WB_UNBOUNDED_FOLLOWING:
+        raise ValueError(f"{who}: a frame cannot start at UNBOUNDED "
+                         "FOLLOWING")
+    if ek == MZ_WB_UNBOUNDED_PRECEDING:
+        raise ValueError(f"{who}: a frame cannot end at UNBOUNDED PRECEDING")
+    if sk == MZ_WB_CURRENT_ROW and ek == PREC:
+        raise ValueError(f"{who}: a frame starting at CURRENT ROW cannot "
+                         "end PRECEDING")
+    if sk == FOLL and ek in (PREC, MZ_WB_CURRENT_ROW):
+        raise ValueError(f"{who}: a frame starting FOLLOWING cannot end "
+                         "PRECEDING or at CURRENT ROW")
+    if (f.offset and sk not in (PREC, FOLL)) or \
+            (f.end_offset and ek not in (PREC, FOLL)):
+        raise ValueError(f"{who}: an offset on an UNBOUNDED or CURRENT ROW "
+                         "bound")
+    if f.func in (MZ_WF_MIN, MZ_WF_MAX) and \
+            sk != MZ_WB_UNBOUNDED_PRECEDING and \
+            ek != MZ_WB_UNBOUNDED_FOLLOWING:
+        raise ValueError(f"{who}: MIN / MAX over a ROWS frame bounded on "
+                         "both sides is not provided (it needs a "
+                         "range-minimum structure)")
+
+
 def window_spec(in_schema, order, funcs, out=None):
     """mz_gpu_window_spec over rows of `in_schema`: `order` a list of
     (off, width, desc) over the val bytes (may be empty), `funcs` 1..4 wf_*
@@ -447,9 +581,16 @@ def window_spec(in_schema, order, funcs, out=None):
                              f"in.val_bytes ({vb})")
     ovb = vb
     for i, f in enumerate(funcs):
+        if wf_is_agg(f.func):
+            _window_agg_check(f"window: func {i}", f, vb)
+            ovb += wf_slot_bytes(f.func)
+            continue
         if f.func > MZ_WF_LAST_VALUE:
             raise ValueError(f"window: func {i}: unknown func {f.func}")
-        if f.frame > MZ_WF_FRAME_PARTITION:
+        # MZ_WF_FRAME_ROWS is the aggregates' alone
+        if f.frame > MZ_WF_FRAME_ROWS or (
+                f.frame > MZ_WF_FRAME_PARTITION
+                and f.func == MZ_WF_LAST_VALUE):
             raise ValueError(f"window: func {i}: unknown frame {f.frame}")
         if f.frame and f.func != MZ_WF_LAST_VALUE:
             raise ValueError(f"window: func {i}: a frame is for LAST_VALUE "

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "../../include/mz_gpu.h"
+#include "window_spec.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -2422,7 +2423,164 @@ struct WinFuncs {
   u32 n;
   mz_gpu_window_func f[MZ_GPU_MAX_WFUNCS];
 };
-#define WIN_MAX_OVB 64
+
+// Window aggregates (SUM / COUNT / MIN / MAX over a frame). Sums are exact
+// in 128-bit two's complement, two limbs; + and - wrap. A frame's sum is a
+// difference of two values of one global (unsegmented) wrapping prefix,
+// which is exact whenever the true difference fits: |m x| < 2^94 with the
+// multiplicities k_window_check admits, over at most 2^32 rows.
+struct U128 {
+  u64 lo, hi;
+};
+struct U128Add {
+  __host__ __device__ U128 operator()(const U128 &a, const U128 &b) const {
+    U128 r;
+    r.lo = a.lo + b.lo;
+    r.hi = a.hi + b.hi + (r.lo < a.lo ? 1u : 0u);
+    return r;
+  }
+};
+__device__ __forceinline__ U128 d_u128_sub(U128 a, U128 b) {
+  U128 r;
+  r.lo = a.lo - b.lo;
+  r.hi = a.hi - b.hi - (a.lo < b.lo ? 1u : 0u);
+  return r;
+}
+// x * c, x signed and c unsigned
+__device__ __forceinline__ U128 d_u128_mul(i64 x, u64 c) {
+  U128 r;
+  r.lo = (u64)x * c;
+  r.hi = __umul64hi((u64)x, c) - (x < 0 ? c : 0);
+  return r;
+}
+
+// Per ordered row, the scan inputs of one datum: w = m x as 128 bits and
+// c = m, both 0 under a NULL. Either output may be absent.
+__global__ void k_window_sum_terms(const u8 *vals, u32 vb, const i64 *diffs,
+                                   u32 off, u32 width, u32 nullable, u64 n,
+                                   U128 *w, u64 *c) {
+  GRID_STRIDE(i, n) {
+    const u8 *src = vals + i * vb + off;
+    const bool nn = !(nullable && src[width] != 0);
+    const u64 m = (u64)diffs[i];
+    if (w) w[i] = nn ? d_u128_mul(d_read_int(src, (u8)width), m) : U128{0, 0};
+    if (c) c[i] = nn ? m : 0;
+  }
+}
+
+// Per ordered row, the datum for a MIN / MAX scan by partition, the scan's
+// identity under a NULL. reverse: row i is written at n - 1 - i with its
+// partition id beside it, so that a forward scan is the suffix extremum.
+__global__ void k_window_ext_terms(const u8 *vals, u32 vb, const u32 *gid,
+                                   u32 off, u32 width, u32 nullable,
+                                   int is_max, int reverse, u64 n, i64 *x,
+                                   u32 *rgid) {
+  GRID_STRIDE(i, n) {
+    const u8 *src = vals + i * vb + off;
+    const bool nn = !(nullable && src[width] != 0);
+    const i64 ident = is_max ? INT64_MIN : INT64_MAX;
+    const u64 j = reverse ? n - 1 - i : i;
+    x[j] = nn ? d_read_int(src, (u8)width) : ident;
+    if (reverse) rgid[j] = gid[i];
+  }
+}
+
+// What the emit kernel reads per aggregate function, indexed as the spec's
+// functions: w = inclusive prefix of m x (SUM), c = inclusive prefix of
+// m [non-NULL] (absent for COUNT(*) and a datum that cannot be NULL, where
+// it is `pre`), x = MIN / MAX: the extremum of the partition's rows up to
+// each row, or with sfx from each row on, stored at n - 1 - row.
+struct WinAggs {
+  const U128 *w[MZ_GPU_MAX_WFUNCS];
+  const u64 *c[MZ_GPU_MAX_WFUNCS];
+  const i64 *x[MZ_GPU_MAX_WFUNCS];
+  u8 sfx[MZ_GPU_MAX_WFUNCS];
+};
+
+// Exclusive position q of the global expanded sequence, base <= q <= the
+// partition's end: the row *r of [st, e) holding position q - 1 and the
+// number *k >= 1 of its copies before q; q = base is (st, 0).
+__device__ __forceinline__ void d_window_pos(const u64 *pre, u64 st, u64 e,
+                                             u64 base, u64 q, u64 *r,
+                                             u64 *k) {
+  if (q == base) {
+    *r = st;
+    *k = 0;
+    return;
+  }
+  u64 i = d_upper_bound<u64>(pre, st, e, q - 1);
+  if (i >= e) i = e - 1;
+  *r = i;
+  *k = q - (i ? pre[i - 1] : 0);
+}
+
+// One aggregate at position p of partition [st, e) (row i, peer start ps):
+// the frame as [qa, qb) of the global expanded sequence, qa after ka copies
+// of row ra and qb after kb copies of row rb, then differences of the
+// prefixes at its two ends. Returns the slot's i64; *nul its null byte.
+__device__ __forceinline__ u64 d_window_agg(const WinSnap &s,
+                                            const WinAggs &A, u32 f,
+                                            const mz_gpu_window_func &fn,
+                                            u32 vb, u64 i, u64 st, u64 e,
+                                            u64 base, u64 M, u64 p, u64 ps,
+                                            u64 *err, u8 *nul) {
+  u64 ra = st, ka = 0, qa = base, rb = e - 1, qb = base + M;
+  bool empty = false;
+  if (fn.frame == MZ_WF_FRAME_TO_CURRENT) {
+    rb = d_upper_bound<u32>(s.pstart, i + 1, e, (u32)ps) - 1;
+    qb = s.pre[rb];
+  } else if (fn.frame == MZ_WF_FRAME_ROWS && !wf_rows_whole(fn)) {
+    const u32 sk = wf_start_kind(fn), ek = wf_end_kind(fn);
+    i64 a = sk == MZ_WB_UNBOUNDED_PRECEDING ? 0
+            : sk == MZ_WB_PRECEDING         ? (i64)p - (i64)fn.offset
+            : sk == MZ_WB_CURRENT_ROW       ? (i64)p
+                                            : (i64)p + (i64)fn.offset;
+    i64 b = ek == MZ_WB_UNBOUNDED_FOLLOWING ? (i64)M - 1
+            : ek == MZ_WB_PRECEDING         ? (i64)p - (i64)fn.end_offset
+            : ek == MZ_WB_CURRENT_ROW       ? (i64)p
+                                            : (i64)p + (i64)fn.end_offset;
+    if (a < 0) a = 0;
+    if (b > (i64)M - 1) b = (i64)M - 1;
+    empty = a > b;
+    if (!empty) {
+      qa = base + (u64)a;
+      qb = base + (u64)b + 1;
+      u64 k;
+      d_window_pos(s.pre, st, e, base, qa, &ra, &ka);
+      d_window_pos(s.pre, st, e, base, qb, &rb, &k);
+    }
+  }
+  const u64 kb = qb - (rb ? s.pre[rb - 1] : 0);
+  const u8 *va = s.vals + ra * vb + fn.off, *vbp = s.vals + rb * vb + fn.off;
+  const bool nna = !(fn.nullable && va[fn.width] != 0);
+  const bool nnb = !(fn.nullable && vbp[fn.width] != 0);
+  // the frame's non-NULL datums; every position for COUNT(*)
+  u64 cnt = 0;
+  if (!empty) {
+    const u64 *c = A.c[f];
+    if (!c)
+      cnt = qb - qa;
+    else
+      cnt = (rb ? c[rb - 1] : 0) + (nnb ? kb : 0) -
+            ((ra ? c[ra - 1] : 0) + (nna ? ka : 0));
+  }
+  *nul = cnt == 0;
+  if (fn.func == MZ_WF_COUNT) return cnt;
+  if (cnt == 0) return 0;
+  if (fn.func == MZ_WF_SUM) {
+    const U128 *w = A.w[f];
+    U128 hi = rb ? w[rb - 1] : U128{0, 0}, lo = ra ? w[ra - 1] : U128{0, 0};
+    if (nnb) hi = U128Add()(hi, d_u128_mul(d_read_int(vbp, fn.width), kb));
+    if (nna) lo = U128Add()(lo, d_u128_mul(d_read_int(va, fn.width), ka));
+    const U128 d = d_u128_sub(hi, lo);
+    if (d.hi != ((i64)d.lo < 0 ? ~0ull : 0ull)) err[2] = 1;
+    return d.lo;
+  }
+  // MIN / MAX: all copies of a row share a datum
+  if (!A.sfx[f]) return (u64)A.x[f][rb];
+  const u64 r0 = qa < s.pre[ra] ? ra : ra + 1;  // the row holding qa
+  return (u64)A.x[f][s.n - 1 - r0];
+}
 
 // One thread per output row o of nout, written at row obase + o with
 // diff = sign * (expand ? 1 : the row's multiplicity). expand: o is a
@@ -2431,10 +2589,13 @@ struct WinFuncs {
 // and new snapshots write disjoint ranges of one buffer: no atomics, and
 // the output position does not depend on scheduling. The val rows of a
 // block's tile are built in LDS and stored by the whole block, contiguous.
+// AGG: the spec holds an aggregate and A its prefix structures; without,
+// the instantiation is the kernel the other specs always ran.
+template <bool AGG>
 __global__ void __launch_bounds__(BLK)
-k_window_emit(WinSnap s, WinFuncs F, u32 kw, u32 vb, u32 ovb, int expand,
-              u64 nout, u64 obase, u64 t, i64 sign, u64 *okeys, u8 *ovals,
-              u64 *otimes, i64 *odiffs) {
+k_window_emit(WinSnap s, WinFuncs F, WinAggs A, u32 kw, u32 vb, u32 ovb,
+              int expand, u64 nout, u64 obase, u64 t, i64 sign, u64 *okeys,
+              u8 *ovals, u64 *otimes, i64 *odiffs, u64 *err) {
   __shared__ u8 rows[BLK * WIN_MAX_OVB];
   const u64 G = s.gid[s.n - 1];
   for (u64 tile = (u64)blockIdx.x * BLK; tile < nout;
@@ -2466,6 +2627,11 @@ k_window_emit(WinSnap s, WinFuncs F, u32 kw, u32 vb, u32 ovb, int expand,
           x = (ps == st ? 0 : s.pre[ps - 1] - base) + 1;
         } else if (fn.func == MZ_WF_DENSE_RANK) {
           x = (u64)(s.pcum[i] - s.pcum[st]) + 1;
+        } else if (AGG && wf_is_agg(fn.func)) {
+          u8 nul;
+          x = d_window_agg(s, A, f, fn, vb, i, st, e, base, M, p, ps, err,
+                           &nul);
+          if (fn.func != MZ_WF_COUNT) row[w + 8] = nul;
         } else {
           u64 r = st;  // FIRST_VALUE
           bool have = true;
@@ -2495,7 +2661,8 @@ k_window_emit(WinSnap s, WinFuncs F, u32 kw, u32 vb, u32 ovb, int expand,
           row[w + 8] = nul;
         }
         for (u32 b = 0; b < 8; b++) row[w + b] = (u8)(x >> (8 * b));
-        w += fn.func <= MZ_WF_DENSE_RANK ? 8 : 9;
+        w += AGG ? wf_slot_bytes(fn.func)
+                 : (fn.func <= MZ_WF_DENSE_RANK ? 8u : 9u);
       }
       for (u32 k = 0; k < kw; k++)
         okeys[(obase + o) * kw + k] = s.keys[i * kw + k];
@@ -3033,8 +3200,12 @@ struct mz_gpu_topk {
 struct mz_gpu_window {
   mz_gpu_window_spec spec;
   mz_gpu_arr *arr = nullptr;  // owned partition-contents arrangement
-  u64 *d_err = nullptr;       // [0] negative count, [1] a count > 2^31 - 1
-  bool expand = false;        // ROW_NUMBER / LAG / LEAD: one row per copy
+  u64 *d_err = nullptr;       // [0] negative count, [1] a count > 2^31 - 1,
+                              // [2] a SUM outside int64
+  bool expand = false;        // ROW_NUMBER / LAG / LEAD / a ROWS aggregate:
+                              // one row per copy
+  bool has_agg = false;       // SUM / COUNT / MIN / MAX: prefixes are built
+  bool has_sum = false;       // [1] fails the push without expansion too
 };
 
 namespace {
@@ -6955,52 +7126,7 @@ int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
 
 // ------------------------------------------------------ window functions
 
-static inline bool wf_is_value(u8 func) { return func >= MZ_WF_LAG; }
-static inline u32 wf_slot_bytes(u8 func) { return wf_is_value(func) ? 9 : 8; }
-
-// The create-time rules of mz_gpu.h; "" when the spec is acceptable.
-static std::string window_spec_error(const mz_gpu_window_spec *sp) {
-  const u32 vb = sp->in.val_bytes;
-  if (is_varlen(vb) || is_varlen(sp->out.val_bytes))
-    return "varlen vals unsupported";
-  if (sp->in.key_words < 1 || sp->in.key_words > 2)
-    return "key_words must be 1 or 2";
-  if (sp->n_funcs < 1 || sp->n_funcs > MZ_GPU_MAX_WFUNCS)
-    return "n_funcs must be 1.." + std::to_string(MZ_GPU_MAX_WFUNCS);
-  if (sp->n_order > MZ_GPU_MAX_ORDER)
-    return "n_order must be at most " + std::to_string(MZ_GPU_MAX_ORDER);
-  for (u32 j = 0; j < sp->n_order; j++) {
-    const mz_gpu_order_col &oc = sp->order[j];
-    std::string who = "order column " + std::to_string(j);
-    if (oc.width != 4 && oc.width != 8) return who + ": width must be 4 or 8";
-    if ((u32)oc.off + oc.width > vb) return who + " reads past in.val_bytes";
-  }
-  u64 ovb = vb;
-  for (u32 f = 0; f < sp->n_funcs; f++) {
-    const mz_gpu_window_func &fn = sp->funcs[f];
-    std::string who = "func " + std::to_string(f);
-    if (fn.func > MZ_WF_LAST_VALUE)
-      return who + ": unknown func " + std::to_string(fn.func);
-    if (fn.frame > MZ_WF_FRAME_PARTITION)
-      return who + ": unknown frame " + std::to_string(fn.frame);
-    if (fn.frame && fn.func != MZ_WF_LAST_VALUE)
-      return who + ": a frame is for LAST_VALUE only";
-    if (wf_is_value(fn.func)) {
-      if (fn.width != 4 && fn.width != 8)
-        return who + ": datum width must be 4 or 8";
-      if ((u32)fn.off + fn.width + (fn.nullable ? 1u : 0u) > vb)
-        return who + " reads past in.val_bytes";
-    }
-    ovb += wf_slot_bytes(fn.func);
-  }
-  if (ovb > WIN_MAX_OVB)
-    return "out val is " + std::to_string(ovb) + " bytes, more than " +
-           std::to_string(WIN_MAX_OVB);
-  if (sp->out.key_words != sp->in.key_words || sp->out.val_bytes != ovb)
-    return "out schema must be in.key_words key words and " +
-           std::to_string(ovb) + " val bytes (in val ++ slots)";
-  return "";
-}
+// The create-time rules (window_spec_error) are in window_spec.h.
 
 mz_gpu_window *mz_gpu_window_create(mz_gpu_ctx *c,
                                     const mz_gpu_window_spec *spec) {
@@ -7013,12 +7139,13 @@ mz_gpu_window *mz_gpu_window_create(mz_gpu_ctx *c,
   mz_gpu_window *r = new mz_gpu_window();
   r->spec = *spec;
   for (u32 f = 0; f < spec->n_funcs; f++) {
-    u8 fn = spec->funcs[f].func;
-    r->expand |= fn == MZ_WF_ROW_NUMBER || fn == MZ_WF_LAG || fn == MZ_WF_LEAD;
+    r->expand |= wf_expands(spec->funcs[f]);
+    r->has_agg |= wf_is_agg(spec->funcs[f].func);
+    r->has_sum |= spec->funcs[f].func == MZ_WF_SUM;
   }
   r->arr = mz_gpu_arr_create(c, &spec->in);
-  r->d_err = dnew<u64>(ctx, 2);
-  fill_u64(ctx, r->d_err, 2, 0);
+  r->d_err = dnew<u64>(ctx, 3);
+  fill_u64(ctx, r->d_err, 3, 0);
   return r;
 }
 
@@ -7031,7 +7158,99 @@ void mz_gpu_window_drop(mz_gpu_ctx *c, mz_gpu_window *op) {
 // Order one eval set of pe->n >= 1 rows as TopK does and derive what the
 // emit kernel reads: peer head flags, their max-scan (peer-start rows) and
 // their sum-scan (dense ranks). All in scratch.
-static WinSnap window_eval(Ctx *ctx, mz_gpu_window *op, mz_gpu_out *pe) {
+// The aggregates' prefix structures over one ordered snapshot, in scratch:
+// per SUM datum the wrapping 128-bit prefix of m x, per nullable datum the
+// prefix of m [non-NULL], per MIN / MAX the extremum scanned by partition
+// from whichever end of the partition its frame is anchored at. Functions
+// over the same datum share them.
+static WinAggs window_agg_prefixes(Ctx *ctx, const mz_gpu_window_spec &sp,
+                                   const OrderedSnap &s, u64 n) {
+  auto &S = (*ctx->scr);
+  const u32 vb = sp.in.val_bytes;
+  WinAggs A{};
+  u32 *rgid = nullptr;
+  auto same_datum = [&](u32 f, u32 g) {
+    const mz_gpu_window_func &a = sp.funcs[f], &b = sp.funcs[g];
+    return wf_is_agg(b.func) && a.off == b.off && a.width == b.width &&
+           !a.nullable == !b.nullable;
+  };
+  for (u32 f = 0; f < sp.n_funcs; f++) {
+    const mz_gpu_window_func &fn = sp.funcs[f];
+    if (!wf_is_agg(fn.func)) continue;
+    const bool want_w = fn.func == MZ_WF_SUM;
+    const bool want_c = fn.nullable != 0;  // COUNT(*) has no null byte
+    for (u32 g = 0; g < f; g++) {
+      if (!same_datum(f, g)) continue;
+      if (want_w && !A.w[f]) A.w[f] = A.w[g];
+      if (want_c && !A.c[f]) A.c[f] = A.c[g];
+    }
+    U128 *wt = want_w && !A.w[f] ? (U128 *)S.get(n * 16) : nullptr;
+    u64 *ct = want_c && !A.c[f] ? (u64 *)S.get(n * 8) : nullptr;
+    if (wt || ct)
+      hipLaunchKernelGGL(k_window_sum_terms, dim3(ngrid(n)), dim3(BLK), 0,
+                         ctx->stream, s.vals, vb, s.diffs, (u32)fn.off,
+                         (u32)fn.width, (u32)fn.nullable, n, wt, ct);
+    if (wt) {
+      U128 *w = (U128 *)S.get(n * 16);
+      size_t need = 0;
+      (void)rocprim::inclusive_scan(nullptr, need, wt, w, n, U128Add(),
+                                    ctx->stream);
+      void *tmp = S.get(need);
+      (void)rocprim::inclusive_scan(tmp, need, wt, w, n, U128Add(),
+                                    ctx->stream);
+      A.w[f] = w;
+    }
+    if (ct) {
+      u64 *c = (u64 *)S.get(n * 8);
+      inclusive_scan_u64(ctx, ct, c, n);
+      A.c[f] = c;
+    }
+    if (fn.func != MZ_WF_MIN && fn.func != MZ_WF_MAX) continue;
+    const bool is_max = fn.func == MZ_WF_MAX;
+    A.sfx[f] = fn.frame == MZ_WF_FRAME_ROWS &&
+               wf_end_kind(fn) == MZ_WB_UNBOUNDED_FOLLOWING &&
+               wf_start_kind(fn) != MZ_WB_UNBOUNDED_PRECEDING;
+    for (u32 g = 0; g < f && !A.x[f]; g++)
+      if (same_datum(f, g) && sp.funcs[g].func == fn.func &&
+          A.sfx[g] == A.sfx[f])
+        A.x[f] = A.x[g];
+    if (A.x[f]) continue;
+    i64 *xt = (i64 *)S.get(n * 8), *x = (i64 *)S.get(n * 8);
+    if (A.sfx[f] && !rgid) rgid = (u32 *)S.get(n * 4);
+    hipLaunchKernelGGL(k_window_ext_terms, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, s.vals, vb, s.g.gid, (u32)fn.off,
+                       (u32)fn.width, (u32)fn.nullable, is_max ? 1 : 0,
+                       A.sfx[f] ? 1 : 0, n, xt, rgid);
+    const u32 *keys = A.sfx[f] ? rgid : s.g.gid;
+    size_t need = 0;
+    if (is_max) {
+      (void)rocprim::inclusive_scan_by_key(nullptr, need, keys, xt, x, n,
+                                           rocprim::maximum<i64>(),
+                                           rocprim::equal_to<u32>(),
+                                           ctx->stream);
+      void *tmp = S.get(need);
+      (void)rocprim::inclusive_scan_by_key(tmp, need, keys, xt, x, n,
+                                           rocprim::maximum<i64>(),
+                                           rocprim::equal_to<u32>(),
+                                           ctx->stream);
+    } else {
+      (void)rocprim::inclusive_scan_by_key(nullptr, need, keys, xt, x, n,
+                                           rocprim::minimum<i64>(),
+                                           rocprim::equal_to<u32>(),
+                                           ctx->stream);
+      void *tmp = S.get(need);
+      (void)rocprim::inclusive_scan_by_key(tmp, need, keys, xt, x, n,
+                                           rocprim::minimum<i64>(),
+                                           rocprim::equal_to<u32>(),
+                                           ctx->stream);
+    }
+    A.x[f] = x;
+  }
+  return A;
+}
+
+static WinSnap window_eval(Ctx *ctx, mz_gpu_window *op, mz_gpu_out *pe,
+                           WinAggs *aggs) {
   u64 n = pe->n;
   u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
   auto &S = (*ctx->scr);
@@ -7056,6 +7275,7 @@ static WinSnap window_eval(Ctx *ctx, mz_gpu_window *op, mz_gpu_out *pe) {
                                 rocprim::maximum<u32>(), ctx->stream);
   u32 *pcum = (u32 *)S.get(n * 4);
   inclusive_scan_u32(ctx, flags, pcum, n);
+  if (op->has_agg) *aggs = window_agg_prefixes(ctx, op->spec, s, n);
   return WinSnap{s.keys, s.vals, s.pre, s.g.gid, s.g.starts, pstart, pcum, n};
 }
 
@@ -7097,7 +7317,17 @@ int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
   std::vector<u64> segn;
   u64 total = 0;
   int rc = 0;
-  bool negative = false, too_big = false;
+  bool negative = false, too_big = false, sum_range = false;
+  // the error words once everything queued has run: a spec holding SUM
+  // needs [1] without expansion too, and [2] is the emit kernels' own
+  auto read_errs = [&]() {
+    const u64 *e = (const u64 *)d2h_pinned(ctx, op->d_err, 24);
+    negative = e[0] != 0;
+    if (op->has_sum) {
+      too_big = too_big || e[1] != 0;
+      sum_range = e[2] != 0;
+    }
+  };
   for (auto [lo, hi, t] : slices) {
     u64 m = hi - lo;
     Groups g = group_sorted(ctx, sk + lo * kw, kw, stm + lo, m);
@@ -7132,8 +7362,9 @@ int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
     }
     if (!rc) {
       WinSnap so{}, sn{};
-      if (oldp->n) so = window_eval(ctx, op, oldp);
-      if (newp->n) sn = window_eval(ctx, op, newp);
+      WinAggs ao{}, an{};
+      if (oldp->n) so = window_eval(ctx, op, oldp, &ao);
+      if (newp->n) sn = window_eval(ctx, op, newp, &an);
       u64 mo = oldp->n, mn = newp->n;  // output rows of each snapshot
       if (op->expand) {
         // the expanded sizes are read back before anything of that size is
@@ -7157,16 +7388,18 @@ int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
       }
       if (!negative && !too_big && mo + mn) {
         FlatCols seg = flat_alloc(ctx, mo + mn, kw, ovb);
+        auto emit = op->has_agg ? k_window_emit<true> : k_window_emit<false>;
         if (mo)
-          hipLaunchKernelGGL(k_window_emit, dim3(ngrid(mo)), dim3(BLK), 0,
-                             ctx->stream, so, F, kw, vb, ovb,
+          hipLaunchKernelGGL(emit, dim3(ngrid(mo)), dim3(BLK), 0,
+                             ctx->stream, so, F, ao, kw, vb, ovb,
                              op->expand ? 1 : 0, mo, (u64)0, t, (i64)-1,
-                             seg.keys, seg.vals, seg.times, seg.diffs);
+                             seg.keys, seg.vals, seg.times, seg.diffs,
+                             op->d_err);
         if (mn)
-          hipLaunchKernelGGL(k_window_emit, dim3(ngrid(mn)), dim3(BLK), 0,
-                             ctx->stream, sn, F, kw, vb, ovb,
+          hipLaunchKernelGGL(emit, dim3(ngrid(mn)), dim3(BLK), 0,
+                             ctx->stream, sn, F, an, kw, vb, ovb,
                              op->expand ? 1 : 0, mn, mo, t, (i64)1, seg.keys,
-                             seg.vals, seg.times, seg.diffs);
+                             seg.vals, seg.times, seg.diffs, op->d_err);
         segs.push_back(seg);
         segn.push_back(mo + mn);
         total += mo + mn;
@@ -7182,8 +7415,8 @@ int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
   if (!rc && !negative && !too_big && total > 0xFFFFFFFFull) too_big = true;
   if (!rc && !negative && !too_big) {
     if (total == 0) {
-      negative = *(u64 *)d2h_pinned(ctx, op->d_err, 8) != 0;
-      if (!negative) *out = empty_out(ctx, kw, ovb);
+      read_errs();
+      if (!negative && !too_big && !sum_range) *out = empty_out(ctx, kw, ovb);
     } else {
       // one slice (the steady state) is consolidated where it was emitted
       FlatCols all = segs[0];
@@ -7208,9 +7441,9 @@ int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
       DevUpdates pin{all.keys, all.vals, all.times, all.diffs, total};
       u64 Mc;
       FlatCols o = consolidate_dev(ctx, kw, ovb, pin, &Mc);
-      negative = *(u64 *)d2h_pinned(ctx, op->d_err, 8) != 0;
+      read_errs();
       if (segs.size() > 1) flat_free(ctx, all);
-      if (negative)
+      if (negative || too_big || sum_range)
         flat_free(ctx, o);
       else
         *out = make_out(o, Mc, kw, ovb);
@@ -7227,6 +7460,10 @@ int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
   }
   if (too_big) {
     ctx->err = "window: expanded partition exceeds 2^31 rows";
+    return -1;
+  }
+  if (sum_range) {
+    ctx->err = "window: SUM out of int64 range";
     return -1;
   }
   return 0;

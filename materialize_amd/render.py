@@ -689,15 +689,20 @@ def render_mfp(ctx, plan: MfpPlan) -> MfpOp:
 class WindowPlan:
     """Window functions over one partitioned, ordered input
     (ReducePlan::Basic with AggregateFunc::RowNumber / Rank / DenseRank /
-    LagLead / FirstValue / LastValue): `spec` from abi.window_spec, its
-    functions from the abi.wf_* builders. Partition key = the input key."""
+    LagLead / FirstValue / LastValue, and WindowAggregate over SUM / COUNT /
+    MIN / MAX with the default, whole-partition or ROWS frame): `spec` from
+    abi.window_spec, its functions from the abi.wf_* builders (wf_sum,
+    wf_count, wf_min, wf_max for the aggregates). Partition key = the input
+    key."""
     spec: abi.WindowSpec
 
 
 class WindowOp:
     """build_basic_aggregate for window functions: each push re-evaluates
     the changed partitions and returns new minus old output rows
-    (input val ++ one slot per function), consolidated."""
+    (input val ++ one slot per function), consolidated. A SUM whose frame
+    sum leaves int64 fails the push; the operator may then only be
+    dropped."""
 
     def __init__(self, ctx, plan: WindowPlan):
         if not getattr(ctx, "supports_window", False):

@@ -15,9 +15,17 @@ position of every changed partition, 25 bytes wide), so it is the
 yardstick. The two alternate in one process: 2 warm-up pushes each, then
 --calls timed ones, host clock around the call (both end in the engine's own
 synchronisation; out-batches are released without copying them to the host).
+
+--aggregates puts a window-aggregate spec in the window operator's place,
+same churn and same yardstick: [SUM(x) over the default frame (the running
+total), SUM(x) and COUNT(*) over ROWS 2 PRECEDING..CURRENT ROW, MAX(x) over
+the partition], 43 bytes wide. It adds the prefix scans (one 128-bit, one
+by partition) to each of the two evaluations of a push and two searches per
+ROWS function to every output row.
 Prints one JSON line. Needs a GPU: there is no fallback.
 
     python profiles/window_cost.py [--rows 100000 400000] [--calls 5]
+                                   [--aggregates]
 """
 import argparse
 import json
@@ -37,6 +45,7 @@ def main():
     p.add_argument("--rows", type=int, nargs="+", default=[100_000, 400_000])
     p.add_argument("--calls", type=int, default=5)
     p.add_argument("--seed", type=int, default=11)
+    p.add_argument("--aggregates", action="store_true")
     args = p.parse_args()
     if args.calls + WARMUP > 8:
         raise SystemExit("window_cost: --calls at most 6 (the loaded rows "
@@ -56,8 +65,14 @@ def main():
     gen.manual_seed(args.seed)
     sch = abi.schema(1, 8)
     order = [(0, 8, False)]
-    wspec = abi.window_spec(sch, order,
-                            [abi.wf_row_number(), abi.wf_lag(0, 8, 1)])
+    if args.aggregates:
+        moving = dict(start=abi.preceding(2), end=abi.CURRENT_ROW)
+        funcs = [abi.wf_sum(0, 8), abi.wf_sum(0, 8, **moving),
+                 abi.wf_count(**moving),
+                 abi.wf_max(0, 8, frame=abi.MZ_WF_FRAME_PARTITION)]
+    else:
+        funcs = [abi.wf_row_number(), abi.wf_lag(0, 8, 1)]
+    wspec = abi.window_spec(sch, order, funcs)
     tspec = abi.topk_spec(sch, order, offset=0, limit=-1)
 
     def stats(ms, what):
@@ -121,7 +136,9 @@ def main():
                     window_out_rows=rows_w, topk_out_rows=rows_t,
                     **stats(ms_w, "window_push"), **stats(ms_t, "topk_push"))
 
-    res = {"calls": args.calls, "points": [point(n) for n in args.rows]}
+    res = {"calls": args.calls,
+           "window_spec": "aggregates" if args.aggregates else "rank_lag",
+           "points": [point(n) for n in args.rows]}
     print(json.dumps(res))
     g.close()
 
