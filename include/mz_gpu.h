@@ -538,12 +538,101 @@ int  mz_gpu_peek(mz_gpu_ctx *ctx, mz_gpu_arr *arr, const uint64_t *keys,
  * before the logical compaction frontier (times below it may already have
  * been advanced to it — the reference refuses peeks before `since`); a
  * negative net count without `allow_negative`.
- * Not provided: ORDER BY / LIMIT finishing (the caller's, as the
- * reference's RowSetFinishing is applied outside the index walk) and
- * key-range bounds. */
+ * ORDER BY / LIMIT finishing and key-range bounds are mz_gpu_peek_select's,
+ * below. */
 int  mz_gpu_peek_scan(mz_gpu_ctx *ctx, mz_gpu_arr *arr, uint64_t as_of,
                       const mz_gpu_closure *mfp, int allow_negative,
                       mz_gpu_out **out);
+
+/* Peek with a key range and a finishing (IndexPeek::collect_finished_data,
+ * compute_state.rs: the RowSetFinishing's order and limit + offset applied
+ * while the index is walked, so that what leaves is the size of the answer).
+ *
+ * Range (NULL = all keys): applies to the STORED key, before the mfp,
+ * compared as a signed i64 tuple of the arrangement's key_words words. A key
+ * passes when it is at or above `lo` and at or below `hi`; an exclusive
+ * bound makes that comparison strict, an unbounded side always passes, and
+ * lo > hi is the empty answer, not an error. Only in-range keys are visited:
+ * each batch's sorted keys are searched for the two ends, and the walk covers
+ * the vals between them. stats->scanned_vals is the number of (batch, val)
+ * items walked, stats->rows_matched the consolidated ok rows before
+ * finishing.
+ *
+ * Scan, mfp, consolidation, as_of, the compaction frontier, pending async
+ * inserts, allow_negative and the error stream are mz_gpu_peek_scan's; with
+ * range == NULL and fin == NULL the out-batch is byte-equal to its.
+ *
+ * Finishing (NULL = none), over the consolidated ok rows (key, val, c),
+ * c > 0. Rows are ordered by the order columns in spec order, ties broken
+ * in the canonical (key, val) order. One column
+ * compares as the reference's compare_columns: NULL equals NULL; a NULL is
+ * greater than any datum when nulls_last is set and less otherwise, whatever
+ * `desc` says; two datums compare as signed little-endian integers, reversed
+ * under `desc`; the datum bytes of a NULL are ignored. An order column
+ * addresses the mfp's OUT row (the stored row without an mfp): MZ_SRC_KEY a
+ * key word, MZ_SRC_VAL_LOOKUP the val bytes. Row r then occupies positions
+ * [lo_r, lo_r + c) of the expanded sequence; the positions [offset,
+ * offset + limit) are kept ([offset, inf) when limit < 0; the sum does not
+ * wrap), a row's out diff is the number of its copies kept, rows with none
+ * are dropped, the out time is as_of. The total multiplicity is computed
+ * exactly and a total above INT64_MAX fails the call ("peek_select: total
+ * multiplicity exceeds int64") before anything is emitted. n_order == 0,
+ * offset == 0, limit < 0 is the identity.
+ * The out-batch of a finishing is in FINISHING order, not canonical order:
+ * it must not be fed anywhere as `sorted = 1`.
+ * Finishing does not touch the error stream. The reference fails a peek on
+ * any error row, so the caller checks err_n before it uses the rows. There
+ * is no finishing projection: an ORDER BY column must be in the mfp's
+ * output, and the caller drops it (the mfp is the projection).
+ *
+ * Errors (non-zero return, nothing allocated is kept, message prefixed
+ * "peek_select:"): everything mz_gpu_peek_scan refuses; a bound kind above
+ * 2; a nonzero bound word beyond key_words or on an unbounded side; n_order
+ * above MZ_GPU_MAX_ORDER; an order column whose src is neither MZ_SRC_KEY
+ * nor MZ_SRC_VAL_LOOKUP, a key column that is not width 8, not at a word
+ * boundary inside the out key, or with a null_off, a val column of width
+ * other than 4, 8 or 16 or reading past the out val, a null_off past the
+ * out val or inside its own datum, desc or nulls_last above 1; a finishing
+ * together with allow_negative. */
+enum { MZ_KB_UNBOUNDED = 0, MZ_KB_INCLUSIVE = 1, MZ_KB_EXCLUSIVE = 2 };
+typedef struct {
+  uint8_t lo_kind, hi_kind;      /* MZ_KB_*                                  */
+  int64_t lo[2], hi[2];          /* first key_words words; i64-tuple order   */
+} mz_gpu_key_range;
+
+#define MZ_GPU_NO_NULL 0xFFFFu
+typedef struct {                 /* 8 bytes; ColumnOrder restated            */
+  uint8_t  src;        /* MZ_SRC_KEY | MZ_SRC_VAL_LOOKUP, of the OUT row      */
+  uint8_t  width;      /* val: 4, 8 or 16 (signed LE); key: 8                 */
+  uint8_t  desc;
+  uint8_t  nulls_last;
+  uint16_t off;        /* byte offset; key: 8 * word                          */
+  uint16_t null_off;   /* val byte that is nonzero when the datum is NULL, or
+                          MZ_GPU_NO_NULL. A window value slot and an
+                          mz_gpu_mfp nullable field put it after the datum, a
+                          reduce or collation slot at slot byte 0, before the
+                          value at [8..24)                                    */
+} mz_gpu_peek_order;
+
+typedef struct {
+  uint32_t n_order;              /* 0..MZ_GPU_MAX_ORDER                      */
+  mz_gpu_peek_order order[MZ_GPU_MAX_ORDER];
+  uint64_t offset;
+  int64_t  limit;                /* < 0 = none                               */
+} mz_gpu_finishing;
+
+typedef struct {
+  uint64_t scanned_vals;   /* (batch, val) items the scan walked             */
+  uint64_t rows_matched;   /* consolidated ok rows before finishing          */
+} mz_gpu_peek_stats;
+
+int  mz_gpu_peek_select(mz_gpu_ctx *ctx, mz_gpu_arr *arr, uint64_t as_of,
+                        const mz_gpu_key_range *range,   /* NULL = all keys  */
+                        const mz_gpu_closure *mfp,       /* as mz_gpu_peek_scan */
+                        const mz_gpu_finishing *fin,     /* NULL = none      */
+                        int allow_negative,
+                        mz_gpu_peek_stats *stats,        /* NULL = not wanted */
+                        mz_gpu_out **out);
 
 /* ------------------------------------------------------- temporal filter
  * Replaces the temporal half of MapFilterProject — MfpPlan { lower_bounds,

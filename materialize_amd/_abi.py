@@ -329,6 +329,176 @@ def topk_spec(in_schema, order, offset=0, limit=-1):
     return sp
 
 
+# ------------------------------------------------------------ peek select
+# mz_gpu_peek_select: a full-scan peek with a key range and an ORDER BY /
+# LIMIT / OFFSET finishing (include/mz_gpu.h states the semantics). The
+# rules below are csrc/peek_select_spec.h's, with the same messages.
+MZ_KB_UNBOUNDED, MZ_KB_INCLUSIVE, MZ_KB_EXCLUSIVE = range(3)
+MZ_GPU_NO_NULL = 0xFFFF
+
+
+class KeyRange(C.Structure):
+    """mz_gpu_key_range: bounds on the stored key, i64-tuple order."""
+    _fields_ = [
+        ("lo_kind", C.c_uint8),
+        ("hi_kind", C.c_uint8),
+        ("lo", C.c_int64 * 2),
+        ("hi", C.c_int64 * 2),
+    ]
+
+
+class PeekOrder(C.Structure):
+    """mz_gpu_peek_order: one ORDER BY column of the peek's out row."""
+    _fields_ = [
+        ("src", C.c_uint8),
+        ("width", C.c_uint8),
+        ("desc", C.c_uint8),
+        ("nulls_last", C.c_uint8),
+        ("off", C.c_uint16),
+        ("null_off", C.c_uint16),
+    ]
+
+
+class Finishing(C.Structure):
+    """mz_gpu_finishing: RowSetFinishing's order_by, offset and limit."""
+    _fields_ = [
+        ("n_order", C.c_uint32),
+        ("order", PeekOrder * MZ_GPU_MAX_ORDER),
+        ("offset", C.c_uint64),
+        ("limit", C.c_int64),
+    ]
+
+
+class PeekStats(C.Structure):
+    _fields_ = [("scanned_vals", C.c_uint64), ("rows_matched", C.c_uint64)]
+
+
+def peek_range_error(r, kw):
+    """The range rules for an arrangement of kw key words; "" when fine."""
+    w = "peek_select: range: "
+    if r.lo_kind > MZ_KB_EXCLUSIVE or r.hi_kind > MZ_KB_EXCLUSIVE:
+        bad = r.lo_kind if r.lo_kind > MZ_KB_EXCLUSIVE else r.hi_kind
+        return w + f"unknown bound kind {bad}"
+    for i in range(2):
+        if i >= kw and (r.lo[i] or r.hi[i]):
+            return w + "nonzero bound word beyond key_words"
+        if (r.lo_kind == MZ_KB_UNBOUNDED and r.lo[i]) or \
+                (r.hi_kind == MZ_KB_UNBOUNDED and r.hi[i]):
+            return w + "nonzero bound word on an unbounded side"
+    return ""
+
+
+def _peek_order_why(oc, okw=None, ovb=None):
+    """What is wrong with one order column, as the text that follows
+    "order column J"; without an out schema only the rules that need none."""
+    if oc.src not in (MZ_SRC_KEY, MZ_SRC_VAL_LOOKUP):
+        return ": src must be MZ_SRC_KEY or MZ_SRC_VAL_LOOKUP"
+    if oc.src == MZ_SRC_KEY:
+        if oc.width != 8:
+            return ": a key column must be width 8"
+        if oc.off % 8 or (okw is not None and oc.off >= 8 * okw):
+            return (": a key column must sit at a word boundary inside the "
+                    "out key")
+        if oc.null_off != MZ_GPU_NO_NULL:
+            return ": a key column takes no null_off"
+    else:
+        if oc.width not in (4, 8, 16):
+            return ": width must be 4, 8 or 16"
+        if ovb is not None and oc.off + oc.width > ovb:
+            return " reads past the out val"
+        if oc.null_off != MZ_GPU_NO_NULL:
+            if ovb is not None and oc.null_off >= ovb:
+                return ": null_off is past the out val"
+            if oc.off <= oc.null_off < oc.off + oc.width:
+                return ": null_off is inside its own datum"
+    if oc.desc > 1 or oc.nulls_last > 1:
+        return ": desc and nulls_last must be 0 or 1"
+    return ""
+
+
+def peek_finishing_error(f, okw, ovb, allow_negative=False):
+    """The finishing rules against the out row it orders (okw key words,
+    ovb val bytes); "" when fine."""
+    p = "peek_select: "
+    if f.n_order > MZ_GPU_MAX_ORDER:
+        return p + f"n_order must be at most {MZ_GPU_MAX_ORDER}"
+    for j in range(f.n_order):
+        why = _peek_order_why(f.order[j], okw, ovb)
+        if why:
+            return p + f"order column {j}" + why
+    if allow_negative:
+        return p + "a finishing cannot be combined with allow_negative"
+    return ""
+
+
+def key_range(lo=None, hi=None, lo_inclusive=True, hi_inclusive=True, kw=1):
+    """Bounds on the stored key: lo / hi are an int (kw == 1) or kw ints,
+    None = unbounded on that side."""
+    r = KeyRange()
+
+    def side(bound, inclusive, words):
+        if bound is None:
+            return MZ_KB_UNBOUNDED
+        bound = [bound] if np.isscalar(bound) else list(bound)
+        if len(bound) != kw:
+            raise ValueError(f"peek_select: range: a bound takes {kw} key "
+                             f"words, not {len(bound)}")
+        for i, x in enumerate(bound):
+            words[i] = int(x)
+        return MZ_KB_INCLUSIVE if inclusive else MZ_KB_EXCLUSIVE
+
+    if kw not in (1, 2):
+        raise ValueError("peek_select: range: key_words must be 1 or 2")
+    r.lo_kind = side(lo, lo_inclusive, r.lo)
+    r.hi_kind = side(hi, hi_inclusive, r.hi)
+    why = peek_range_error(r, kw)
+    if why:
+        raise ValueError(why)
+    return r
+
+
+def order_by(src, off, width=8, desc=False, nulls_last=None, null_off=None):
+    """One ORDER BY column of the peek's out row: MZ_SRC_KEY at byte 8 *
+    word, or MZ_SRC_VAL_LOOKUP bytes [off, off + width) as a signed
+    little-endian integer. null_off = the val byte that is nonzero when the
+    datum is NULL. nulls_last=None is the SQL default: last for ASC, first
+    for DESC."""
+    if nulls_last is None:
+        nulls_last = not desc
+    for name, v in (("src", src), ("width", width), ("desc", int(desc)),
+                    ("nulls_last", int(nulls_last))):
+        if not 0 <= v <= 0xFF:
+            raise ValueError(f"peek_select: order column: {name} out of "
+                             "range")
+    oc = PeekOrder(src=src, width=width, desc=int(desc),
+                   nulls_last=int(nulls_last), off=off,
+                   null_off=MZ_GPU_NO_NULL if null_off is None else null_off)
+    why = _peek_order_why(oc)
+    if why:
+        raise ValueError("peek_select: order column" + why)
+    return oc
+
+
+def finishing(order=(), limit=None, offset=0):
+    """ORDER BY `order` (abi.order_by columns) OFFSET `offset` LIMIT `limit`
+    (None = no limit)."""
+    order = list(order)
+    f = Finishing()
+    f.n_order = len(order)
+    for j, oc in enumerate(order[:MZ_GPU_MAX_ORDER]):
+        f.order[j] = oc
+    f.offset = offset
+    f.limit = -1 if limit is None else limit
+    if f.n_order > MZ_GPU_MAX_ORDER:
+        raise ValueError("peek_select: n_order must be at most "
+                         f"{MZ_GPU_MAX_ORDER}")
+    for j, oc in enumerate(order):
+        why = _peek_order_why(oc)
+        if why:
+            raise ValueError(f"peek_select: order column {j}" + why)
+    return f
+
+
 # ------------------------------------------------------ window functions
 # mz_gpu_window_*: ROW_NUMBER, RANK, DENSE_RANK, LAG / LEAD, FIRST_VALUE /
 # LAST_VALUE and the aggregates SUM / COUNT / MIN / MAX over a frame, per

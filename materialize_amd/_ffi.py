@@ -8,9 +8,9 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (Closure, CollationSpec, MfpSpec, OutBatch, ReduceSpec,
-                   Schema, TemporalSpec, TopKSpec, Updates, WindowSpec,
-                   out_to_numpy)
+from ._abi import (Closure, CollationSpec, Finishing, KeyRange, MfpSpec,
+                   OutBatch, PeekStats, ReduceSpec, Schema, TemporalSpec,
+                   TopKSpec, Updates, WindowSpec, out_to_numpy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "csrc", "libmzgpu.so")
@@ -148,6 +148,10 @@ def load():
     lib.mz_gpu_peek_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.POINTER(Closure), C.c_int,
                                      C.POINTER(C.POINTER(OutBatch))]
+    lib.mz_gpu_peek_select.argtypes = [
+        C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(KeyRange),
+        C.POINTER(Closure), C.POINTER(Finishing), C.c_int,
+        C.POINTER(PeekStats), C.POINTER(C.POINTER(OutBatch))]
     lib.mz_gpu_temporal_create.restype = C.c_void_p
     lib.mz_gpu_temporal_create.argtypes = [C.c_void_p,
                                            C.POINTER(TemporalSpec)]
@@ -186,6 +190,10 @@ class GpuCtx:
     # Full-scan peeks (mz_gpu_peek_scan) are implemented here; render_peek
     # refuses contexts that do not say so.
     supports_scan_peek = True
+    # Peeks with a key range and an ORDER BY / LIMIT / OFFSET finishing
+    # (mz_gpu_peek_select) are implemented here; render_peek refuses plans
+    # that need them on contexts that do not say so.
+    supports_peek_select = True
     # Temporal filters (mz_gpu_temporal_*) are implemented here;
     # render_temporal_filter refuses contexts that do not say so.
     supports_temporal_filter = True
@@ -444,6 +452,28 @@ class GpuCtx:
         raises MzGpuError unless `allow_negative`."""
         return self._take(self._peek_scan(arr, as_of, mfp, allow_negative))
 
+    def _peek_select(self, arr, as_of, key_range, mfp, finishing,
+                     allow_negative):
+        outp = C.POINTER(OutBatch)()
+        stats = PeekStats()
+        ref = lambda x: C.byref(x) if x is not None else None
+        self._check(self.lib.mz_gpu_peek_select(
+            self.ctx, arr, as_of, ref(key_range), ref(mfp), ref(finishing),
+            1 if allow_negative else 0, C.byref(stats), C.byref(outp)))
+        self.last_peek_stats = (stats.scanned_vals, stats.rows_matched)
+        return outp
+
+    def peek_select(self, arr, as_of, key_range=None, mfp=None,
+                    finishing=None, allow_negative=False):
+        """peek_scan restricted to the stored keys inside `key_range`
+        (abi.key_range) and finished by `finishing` (abi.finishing: ORDER
+        BY, OFFSET, LIMIT over the mfp's out rows). Host columns like
+        `peek_scan`, in finishing order when there is a finishing; error
+        rows land in self.last_errs untouched by the finishing, and
+        self.last_peek_stats is (scanned vals, rows before finishing)."""
+        return self._take(self._peek_select(arr, as_of, key_range, mfp,
+                                            finishing, allow_negative))
+
     def temporal_create(self, spec):
         op = self.lib.mz_gpu_temporal_create(self.ctx, C.byref(spec))
         if not op:
@@ -547,6 +577,13 @@ class GpuCtx:
         # consolidated output in canonical order
         return self._dev_out(
             self._peek_scan(arr, as_of, mfp, allow_negative), sorted=True)
+
+    def peek_select_dev(self, arr, as_of, key_range=None, mfp=None,
+                        finishing=None, allow_negative=False):
+        # canonical order only without a finishing
+        return self._dev_out(
+            self._peek_select(arr, as_of, key_range, mfp, finishing,
+                              allow_negative), sorted=finishing is None)
 
     def temporal_push_dev(self, op, upd):
         # consolidated output in canonical order

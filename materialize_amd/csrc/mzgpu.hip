@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "../../include/mz_gpu.h"
+#include "peek_select_spec.h"
 #include "window_spec.h"
 
 #include <algorithm>
@@ -6116,21 +6117,262 @@ static std::string mfp_shape_error(const char *who, const mz_gpu_closure *cl,
   return std::string();
 }
 
-// Full-scan peek host path: the probe protocol with
+// ------------------------------------------------------------ peek select
+// The kernels of mz_gpu_peek_select sit here, behind every kernel of the
+// maintenance path, so that adding them leaves those kernels where they
+// were in the code object.
+// Key-range ends of every batch of a peek (mz_gpu_peek_select, range): one
+// thread per (batch, side) binary-searches the batch's sorted keys for the
+// first key at or beyond the bound (lo: the first key that passes; hi: the
+// first that no longer does) and writes, per batch, out[4b + side] = that
+// key's first val index and out[4b + 2 + side] = that val's first update
+// index. kv_off has n_keys + 1 entries and vu_off n_vals + 1, so the end
+// positions are in bounds.
+__global__ void k_peek_range_bounds(BatchList bl, u32 kw,
+                                    const mz_gpu_key_range r, u64 *out) {
+  u32 t = threadIdx.x;
+  if (t >= 2u * (u32)bl.n) return;
+  const DevBatch &b = bl.b[t >> 1];
+  u32 side = t & 1;
+  u32 kind = side ? r.hi_kind : r.lo_kind;
+  static_assert(MAX_KW == 2, "mz_gpu_key_range holds two words");
+  i64 b0 = side ? r.hi[0] : r.lo[0], b1 = side ? r.hi[1] : r.lo[1];
+  u64 idx = side ? b.n_keys : 0;
+  if (kind != MZ_KB_UNBOUNDED) {
+    // skip keys <= bound (strict) or < bound
+    bool strict = side ? kind == MZ_KB_INCLUSIVE : kind == MZ_KB_EXCLUSIVE;
+    u64 lo = 0, hi = b.n_keys;
+    while (lo < hi) {
+      u64 mid = lo + (hi - lo) / 2;
+      const u64 *k = b.keys + mid * kw;
+      i64 x = (i64)k[0], y = b0;
+      if (x == y && kw > 1) x = (i64)k[1], y = b1;
+      int c = x < y ? -1 : x > y ? 1 : 0;  // d_key_cmp against the bound
+      if (strict ? c <= 0 : c < 0)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    idx = lo;
+  }
+  u32 v = b.kv_off[idx];
+  out[4 * (t >> 1) + side] = v;
+  out[4 * (t >> 1) + 2 + side] = b.vu_off[v];
+}
+
+// Exact total of n positive i64 counts without a 128-bit atomic: sums[0]
+// += the counts' high 32 bits, sums[1] += their low 32 bits. Fewer than
+// 2^32 rows keep both sums exact in a u64 (peek_total_fits puts them
+// together). One atomic pair per wave.
+__global__ void k_peek_count_sums(const i64 *diffs, u64 n,
+                                  unsigned long long *sums) {
+  unsigned long long hi = 0, lo = 0;
+  GRID_STRIDE(i, n) {
+    u64 c = (u64)diffs[i];
+    hi += c >> 32;
+    lo += c & 0xFFFFFFFFull;
+  }
+  for (int d = 32; d; d >>= 1) {
+    hi += __shfl_down(hi, d, 64);
+    lo += __shfl_down(lo, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(sums, hi);
+    atomicAdd(sums + 1, lo);
+  }
+}
+
+// Order-preserving u64 radix key of one finishing order column for the row
+// perm[i] (k_order_sortkey extended: key source, NULL rank, 16-byte datums).
+// part 0 = the datum's word (of a 16-byte datum the biased high word),
+// part 1 = the low word of a 16-byte datum, part 2 = the NULL rank: 1 for
+// the side that sorts last. A NULL's datum key is 0 whatever its bytes
+// hold; descending columns invert the datum keys, never the rank.
+enum { PEEK_KEY_DATUM = 0, PEEK_KEY_LOW = 1, PEEK_KEY_NULL = 2 };
+__global__ void k_peek_sortkey(const u64 *keys, u32 kw, const u8 *vals,
+                               u32 vb, const u32 *perm, u64 *skey, u64 n,
+                               const mz_gpu_peek_order oc, u32 part) {
+  GRID_STRIDE(i, n) {
+    u64 r = perm[i];
+    bool null = oc.null_off != MZ_GPU_NO_NULL &&
+                vals[r * vb + oc.null_off] != 0;
+    u64 s = 0;
+    if (part == PEEK_KEY_NULL) {
+      s = null == (oc.nulls_last != 0) ? 1 : 0;
+    } else if (!null) {
+      const u64 sign = 0x8000000000000000ull;
+      if (oc.src == MZ_SRC_KEY) {
+        s = keys[r * kw + oc.off / 8] ^ sign;
+      } else {
+        const u8 *v = vals + r * vb + oc.off;
+        if (oc.width == 4)
+          s = (u64)(i64)(int32_t)(u32)le_val_word(v, 4) ^ sign;
+        else if (oc.width == 8)
+          s = le_val_word(v, 8) ^ sign;
+        else
+          s = part == PEEK_KEY_LOW ? le_val_word(v, 8)
+                                   : le_val_word(v + 8, 8) ^ sign;
+      }
+      if (oc.desc) s = ~s;
+    }
+    skey[i] = s;
+  }
+}
+
+// Copies of ordered row i inside the position window [off, end): the row
+// occupies [pre[i] - c, pre[i]) of the expanded sequence (pre = inclusive
+// scan of the ordered counts c; the total fits an i64, so nothing wraps).
+__device__ __forceinline__ u64 d_peek_kept(const u64 *pre, const i64 *c,
+                                           u64 i, u64 off, u64 end) {
+  u64 hi = pre[i], lo = hi - (u64)c[i];
+  u64 wlo = lo > off ? lo : off, whi = hi < end ? hi : end;
+  return whi > wlo ? whi - wlo : 0;
+}
+
+__global__ void k_peek_kept_flags(const u64 *pre, const i64 *c, u64 n,
+                                  u64 off, u64 end, u32 *flags) {
+  GRID_STRIDE(i, n) flags[i] = d_peek_kept(pre, c, i, off, end) ? 1u : 0u;
+}
+
+// The finishing's clip (k_topk_kept's window, whole result as one group):
+// ordered row i = source row perm[i] (perm == nullptr: row i) leaves with
+// its kept copies at pos[i], its rank among the kept rows, so the out
+// columns are in finishing order.
+__global__ void k_peek_clip_emit(const u64 *keys, u32 kw, const u8 *vals,
+                                 u32 vb, const u32 *perm, const i64 *c,
+                                 const u64 *pre, const u32 *pos, u64 n,
+                                 u64 off, u64 end, u64 t, u64 *okeys,
+                                 u8 *ovals, u64 *otimes, i64 *odiffs) {
+  GRID_STRIDE(i, n) {
+    u64 kept = d_peek_kept(pre, c, i, off, end);
+    if (!kept) continue;
+    u64 r = perm ? perm[i] : i, o = pos[i];
+    for (u32 w = 0; w < kw; w++) okeys[o * kw + w] = keys[r * kw + w];
+    for (u32 b = 0; b < vb; b++) ovals[o * vb + b] = vals[r * vb + b];
+    otimes[o] = t;
+    odiffs[o] = (i64)kept;
+  }
+}
+
+// Narrow a peek's batch snapshot to the vals of the in-range keys
+// (mz_gpu_peek_select, range): k_peek_range_bounds finds every batch's two
+// ends, one readback brings them to the host, and each DevBatch copy in
+// `bl` is moved to its first in-range val. val_key and vu_off hold absolute
+// indices, so keys, times and diffs stay where they are and k_scan_walk
+// runs unchanged over the narrowed list.
+static void peek_narrow_batchlist(Ctx *ctx, const mz_gpu_key_range *range,
+                                  u32 kw, u32 vb, BatchList &bl) {
+  if (bl.n == 0) return;
+  u64 *dends = (u64 *)(*ctx->scr).get(4 * 12 * 8);
+  hipLaunchKernelGGL(k_peek_range_bounds, dim3(1), dim3(64), 0, ctx->stream,
+                     bl, kw, *range, dends);
+  const u64 *e = (const u64 *)d2h_pinned(ctx, dends, 4 * 8 * (size_t)bl.n);
+  for (int i = 0; i < bl.n; i++) {
+    DevBatch &b = bl.b[i];
+    u64 vlo = e[4 * i], vhi = std::max(e[4 * i + 1], vlo);  // lo > hi: empty
+    u64 ulo = e[4 * i + 2], uhi = std::max(e[4 * i + 3], ulo);
+    if (b.vals) b.vals += vlo * vb;
+    b.val_key += vlo;
+    b.vu_off += vlo;
+    b.n_vals = vhi - vlo;
+    b.n_upds = uhi - ulo;
+  }
+}
+
+// The finishing of mz_gpu_peek_select over the n consolidated rows `o`
+// (canonical order, counts > 0): exact total, stable radix passes from the
+// last order column to the first (so ties keep the canonical order), exact
+// scan of the ordered counts, in-order clip. Replaces o and n by the
+// finished rows; returns the message on failure (o is then unchanged).
+static std::string peek_finish(Ctx *ctx, const mz_gpu_finishing *fin, u32 kw,
+                               u32 vb, u64 as_of, FlatCols &o, u64 &n) {
+  auto &S = (*ctx->scr);
+  if (n == 0) return "";
+  unsigned long long *sums = (unsigned long long *)S.get(16);
+  fill_u64(ctx, (u64 *)sums, 2, 0);
+  hipLaunchKernelGGL(k_peek_count_sums, dim3(ngrid(n)), dim3(BLK), 0,
+                     ctx->stream, o.diffs, n, sums);
+  const u64 *hs = (const u64 *)d2h_pinned(ctx, sums, 16);
+  u64 total;
+  if (!peek_total_fits(hs[0], hs[1], &total))
+    return "peek_select: total multiplicity exceeds int64";
+  if (peek_finishing_is_identity(fin)) return "";
+  const u32 *perm = nullptr;
+  const i64 *cnt = o.diffs;
+  if (fin->n_order) {
+    u32 *p = (u32 *)S.get(n * 4), *p_out = (u32 *)S.get(n * 4);
+    u64 *skey = (u64 *)S.get(n * 8), *skey_out = (u64 *)S.get(n * 8);
+    hipLaunchKernelGGL(k_iota, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream, p,
+                       n);
+    size_t tmp_bytes = 0, tmp_bytes1 = 0;  // full-word and NULL-rank passes
+    (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes, skey, skey_out, p,
+                                    p_out, (unsigned)n, 0, 64, ctx->stream);
+    (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes1, skey, skey_out, p,
+                                    p_out, (unsigned)n, 0, 1, ctx->stream);
+    tmp_bytes = std::max(tmp_bytes, tmp_bytes1);
+    void *tmp = S.get(tmp_bytes);
+    auto pass = [&](const mz_gpu_peek_order &oc, u32 part) {
+      hipLaunchKernelGGL(k_peek_sortkey, dim3(ngrid(n)), dim3(BLK), 0,
+                         ctx->stream, o.keys, kw, o.vals, vb, p, skey, n, oc,
+                         part);
+      size_t nb = tmp_bytes;
+      (void)rocprim::radix_sort_pairs(tmp, nb, skey, skey_out, p, p_out,
+                                      (unsigned)n, 0,
+                                      part == PEEK_KEY_NULL ? 1 : 64,
+                                      ctx->stream);
+      std::swap(p, p_out);
+    };
+    for (int j = (int)fin->n_order - 1; j >= 0; j--) {
+      const mz_gpu_peek_order &oc = fin->order[j];
+      if (oc.src != MZ_SRC_KEY && oc.width == 16) pass(oc, PEEK_KEY_LOW);
+      pass(oc, PEEK_KEY_DATUM);
+      if (oc.null_off != MZ_GPU_NO_NULL) pass(oc, PEEK_KEY_NULL);
+    }
+    i64 *sd = (i64 *)S.get(n * 8);
+    hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, o.diffs, p, sd, n);
+    perm = p;
+    cnt = sd;
+  }
+  u64 *pre = (u64 *)S.get(n * 8);
+  inclusive_scan_u64(ctx, (const u64 *)cnt, pre, n);
+  u64 end = peek_window_end(fin->offset, fin->limit);
+  u32 *flags = (u32 *)S.get(n * 4), *pos = (u32 *)S.get((n + 1) * 4);
+  hipLaunchKernelGGL(k_peek_kept_flags, dim3(ngrid(n)), dim3(BLK), 0,
+                     ctx->stream, pre, cnt, n, fin->offset, end, flags);
+  u64 K = exclusive_scan_u32(ctx, flags, pos, n);
+  FlatCols f = flat_alloc(ctx, K, kw, vb);
+  if (K)
+    hipLaunchKernelGGL(k_peek_clip_emit, dim3(ngrid(n)), dim3(BLK), 0,
+                       ctx->stream, o.keys, kw, o.vals, vb, perm, cnt, pre,
+                       pos, n, fin->offset, end, as_of, f.keys, f.vals,
+                       f.times, f.diffs);
+  flat_free(ctx, o);
+  o = f;
+  n = K;
+  return "";
+}
+
+// Peek host path (mz_gpu_peek_scan; mz_gpu_peek_select adds a key range, a
+// finishing and statistics): the probe protocol with
 // k_scan_walk as the launch — prepare, snapshot, run_probe, consolidate,
-// negative-count check, error stream.
-static int peek_scan_impl(Ctx *ctx, mz_gpu_arr *arr, u64 as_of,
-                          const mz_gpu_closure *mfp, int allow_negative,
-                          mz_gpu_out **out) {
+// negative-count check, finishing, error stream. `who` prefixes the
+// messages.
+static int peek_scan_impl(Ctx *ctx, const char *who, mz_gpu_arr *arr,
+                          u64 as_of, const mz_gpu_key_range *range,
+                          const mz_gpu_closure *mfp,
+                          const mz_gpu_finishing *fin, int allow_negative,
+                          mz_gpu_peek_stats *stats, mz_gpu_out **out) {
+  const std::string w = std::string(who) + ": ";
   if (is_varlen(arr->schema.vb)) {
-    ctx->err = "peek_scan: varlen arrangements unsupported";
+    ctx->err = w + "varlen arrangements unsupported";
     return 1;
   }
   u32 kw = arr->schema.kw, vb = arr->schema.vb;
   mz_gpu_closure cl{};
   if (mfp) {
     std::string why = mfp_shape_error(
-        "peek_scan", mfp, kw, vb, MZ_SRC_VAL_STREAM,
+        who, mfp, kw, vb, MZ_SRC_VAL_STREAM,
         "MZ_SRC_VAL_STREAM (a scan has no stream side)",
         "the arrangement's key or val");
     if (!why.empty()) {
@@ -6148,22 +6390,33 @@ static int peek_scan_impl(Ctx *ctx, mz_gpu_arr *arr, u64 as_of,
     cl.out.key_words = kw;
     cl.out.val_bytes = vb;
   }
+  u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  {
+    std::string why = range ? peek_range_error(range, kw) : "";
+    if (why.empty() && fin)
+      why = peek_finishing_error(fin, okw, ovb, allow_negative);
+    if (!why.empty()) {
+      ctx->err = why;
+      return 1;
+    }
+  }
   if (as_of == ~0ull) {  // as_of + 1 is the probe's exclusive bound
-    ctx->err = "peek_scan: as_of out of range";
+    ctx->err = w + "as_of out of range";
     return 1;
   }
   if (as_of < arr->logical_compaction) {
-    ctx->err = "peek_scan: as_of " + std::to_string(as_of) +
+    ctx->err = w + "as_of " + std::to_string(as_of) +
                " is before the compaction frontier " +
                std::to_string(arr->logical_compaction);
     return 1;
   }
-  u32 okw = cl.out.key_words, ovb = cl.out.val_bytes;
+  if (stats) *stats = mz_gpu_peek_stats{0, 0};
   // a pending insert wholly beyond as_of keeps running on its lane
   probe_prepare(ctx, arr, PM_HALF_LE, as_of + 1);
   BatchList bl;
   build_probe_batchlist(ctx, arr, as_of + 1, bl);
   (*ctx->scr).reset();
+  if (range) peek_narrow_batchlist(ctx, range, kw, vb, bl);
   ScanBases vbase;
   u64 n = 0, n_upds = 0;
   for (int b = 0; b < bl.n; b++) {
@@ -6209,8 +6462,18 @@ static int peek_scan_impl(Ctx *ctx, mz_gpu_arr *arr, u64 as_of,
     if (neg) {
       flat_free(ctx, o);
       pq.free_errs(ctx);
-      ctx->err = "peek_scan: negative multiplicity (" + std::to_string(neg) +
+      ctx->err = w + "negative multiplicity (" + std::to_string(neg) +
                  " rows)";
+      return 1;
+    }
+  }
+  if (stats) *stats = mz_gpu_peek_stats{n, Mc};
+  if (fin) {
+    std::string why = peek_finish(ctx, fin, okw, ovb, as_of, o, Mc);
+    if (!why.empty()) {
+      flat_free(ctx, o);
+      pq.free_errs(ctx);
+      ctx->err = why;
       return 1;
     }
   }
@@ -6223,7 +6486,17 @@ static int peek_scan_impl(Ctx *ctx, mz_gpu_arr *arr, u64 as_of,
 int mz_gpu_peek_scan(mz_gpu_ctx *c, mz_gpu_arr *arr, uint64_t as_of,
                      const mz_gpu_closure *mfp, int allow_negative,
                      mz_gpu_out **out) {
-  return peek_scan_impl(&c->impl, arr, as_of, mfp, allow_negative, out);
+  return peek_scan_impl(&c->impl, "peek_scan", arr, as_of, nullptr, mfp,
+                        nullptr, allow_negative, nullptr, out);
+}
+
+int mz_gpu_peek_select(mz_gpu_ctx *c, mz_gpu_arr *arr, uint64_t as_of,
+                       const mz_gpu_key_range *range,
+                       const mz_gpu_closure *mfp,
+                       const mz_gpu_finishing *fin, int allow_negative,
+                       mz_gpu_peek_stats *stats, mz_gpu_out **out) {
+  return peek_scan_impl(&c->impl, "peek_select", arr, as_of, range, mfp, fin,
+                        allow_negative, stats, out);
 }
 
 // ------------------------------------------------------ temporal filter

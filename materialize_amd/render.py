@@ -565,27 +565,52 @@ def _check_peek_mfp(mfp):
 
 @dataclass
 class PeekPlan:
-    """A full-scan peek of an index (compute_state.rs IndexPeek without
-    literal constraints): `schema` is the arrangement's, `mfp` the peek's
+    """A peek of an index (compute_state.rs IndexPeek without literal
+    constraints): `schema` is the arrangement's, `mfp` the peek's
     map_filter_project as a closure over (MZ_SRC_KEY, MZ_SRC_VAL_LOOKUP),
-    None for the rows as stored. ORDER BY / LIMIT finishing
-    (RowSetFinishing) stays with the caller."""
+    None for the rows as stored. `key_range` (abi.key_range) bounds the
+    stored keys the walk visits; `finishing` (abi.finishing) is the
+    RowSetFinishing — ORDER BY, OFFSET, LIMIT over the mfp's out rows (the
+    stored rows without an mfp), applied on the device. With neither, the
+    plan is the full-scan peek and finishing stays with the caller."""
     schema: abi.Schema
     mfp: Optional[abi.Closure] = None
     allow_negative: bool = False
+    key_range: Optional[abi.KeyRange] = None
+    finishing: Optional[abi.Finishing] = None
 
     def __post_init__(self):
         if self.schema.val_bytes == abi.MZ_GPU_VARLEN:
             raise ValueError("PeekPlan: varlen arrangements unsupported")
         if self.mfp is not None:
             _check_peek_mfp(self.mfp)
+        out = self.schema if self.mfp is None else self.mfp.out
+        why = ""
+        if self.key_range is not None:
+            why = abi.peek_range_error(self.key_range, self.schema.key_words)
+        if not why and self.finishing is not None:
+            why = abi.peek_finishing_error(self.finishing, out.key_words,
+                                           out.val_bytes,
+                                           self.allow_negative)
+        if why:
+            raise ValueError("PeekPlan: " + why)
+
+    @property
+    def selects(self):
+        """Does the plan need mz_gpu_peek_select?"""
+        return self.key_range is not None or self.finishing is not None
 
 
 class PeekOp:
-    """handle_peek over a whole index: read(as_of) is the arrangement's
-    content as of that time, consolidated, in canonical order."""
+    """handle_peek over an index: read(as_of) is the arrangement's content
+    as of that time, consolidated, in canonical order — or, for a plan with
+    a finishing, the finished rows in finishing order."""
 
     def __init__(self, ctx, arr, plan: PeekPlan):
+        if plan.selects and not getattr(ctx, "supports_peek_select", False):
+            raise NotImplementedError(
+                "this context does not implement key ranges and finishing "
+                "on a peek (peek select)")
         if not getattr(ctx, "supports_scan_peek", False):
             raise NotImplementedError(
                 "this context does not implement the full-scan peek "
@@ -595,8 +620,13 @@ class PeekOp:
         self.plan = plan
 
     def read(self, as_of) -> DevOut:
-        return self.ctx.peek_scan_dev(self.arr, as_of, self.plan.mfp,
-                                      self.plan.allow_negative)
+        p = self.plan
+        if p.selects:
+            return self.ctx.peek_select_dev(self.arr, as_of, p.key_range,
+                                            p.mfp, p.finishing,
+                                            p.allow_negative)
+        return self.ctx.peek_scan_dev(self.arr, as_of, p.mfp,
+                                      p.allow_negative)
 
 
 def render_peek(ctx, arr, plan: PeekPlan) -> PeekOp:

@@ -102,6 +102,16 @@ def q3_reduce_plan():
     return ReducePlan(abi.reduce_spec(aggs, abi.schema(2, 8)))
 
 
+def q3_top10():
+    """Q3's `ORDER BY revenue DESC, o_orderdate LIMIT 10` over the output
+    index's rows: the SUM slot's i128 at val bytes [8, 24) with its null
+    byte at 0, then key word 1 (o_orderdate in its low half, under
+    o_shippriority, which TPC-H holds at 0), then o_orderkey."""
+    return abi.finishing(
+        [abi.order_by(VL, 8, width=16, desc=True, null_off=0),
+         abi.order_by(KEY, 8), abi.order_by(KEY, 0)], limit=10)
+
+
 class Q3Dataflow:
     """TPC-H Q3 maintained incrementally: 3-path delta join + accumulable
     SUM reduce, all arrangements engine-resident. Works over any engine
@@ -142,11 +152,20 @@ class Q3Dataflow:
         if self.arr_out is not None and corr.n:
             self.ctx.arr_insert(self.arr_out, corr.updates(t, t + 1))
 
-    def peek_result(self, t):
-        """The view's rows as of t (host columns), from the output index."""
+    def peek_result(self, t, finishing=None, key_range=None):
+        """The view's rows as of t (host columns), from the output index.
+        `finishing` (abi.finishing) and `key_range` (abi.key_range, over
+        (l_orderkey, o_orderdate | o_shippriority)) make it a peek select;
+        Q3's own `ORDER BY revenue DESC, ... LIMIT 10` is q3_top10()."""
         if self.out_peek is None:
             raise ValueError("Q3Dataflow was built without index_output")
-        out = self.out_peek.read(t)
+        peek = self.out_peek
+        if finishing is not None or key_range is not None:
+            peek = render_peek(self.ctx, self.arr_out,
+                               PeekPlan(self.out_peek.plan.schema,
+                                        key_range=key_range,
+                                        finishing=finishing))
+        out = peek.read(t)
         cols = out.to_host()
         out.release()
         return cols
