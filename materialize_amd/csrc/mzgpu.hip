@@ -4083,8 +4083,9 @@ std::vector<TimeSlice> time_slices(Ctx *c, const u64 *stm, u64 n, u64 lower,
   return slices;
 }
 
-// Sort n updates by (time, key) and materialize the sorted columns in
-// scratch (vals only when vb != 0).
+// Sort n updates by (time, key) and materialize the sorted columns (vals
+// only when vb != 0): in scratch, or in the caller's owned columns `into`
+// (room for n rows) when they must outlive a scratch reset.
 struct SortedCols {
   u64 *keys;
   u8 *vals;
@@ -4092,17 +4093,59 @@ struct SortedCols {
   i64 *diffs;
 };
 SortedCols sort_gather(Ctx *c, const u64 *keys, u32 kw, const u8 *vals,
-                       u32 vb, const u64 *times, const i64 *diffs, u64 n) {
+                       u32 vb, const u64 *times, const i64 *diffs, u64 n,
+                       const FlatCols *into = nullptr) {
   auto &S = (*c->scr);
   u32 *perm = (u32 *)S.get(n * 4);
   sort_updates(c, keys, kw, vals, vb, times, n, perm, true);
-  SortedCols s{(u64 *)S.get(n * kw * 8), (u8 *)S.get(std::max<u64>(n * vb, 1)),
-               (u64 *)S.get(n * 8), (i64 *)S.get(n * 8)};
+  SortedCols s =
+      into ? SortedCols{into->keys, into->vals, into->times, into->diffs}
+           : SortedCols{(u64 *)S.get(n * kw * 8),
+                        (u8 *)S.get(std::max<u64>(n * vb, 1)),
+                        (u64 *)S.get(n * 8), (i64 *)S.get(n * 8)};
   hipLaunchKernelGGL(k_gather_updates, dim3(ngrid(n)), dim3(BLK), 0,
                      c->stream, keys, kw, vals, vb, times, diffs, perm, s.keys,
                      s.vals, s.times, s.diffs, n);
   return s;
 }
+
+// Stable LSD radix passes over a permutation of n rows, all in scratch.
+// Starting from the identity, per sort column (least significant first) the
+// caller writes the column's keys in perm() order into skey() and calls
+// pass(), which sorts the permutation by the keys' low end_bit bits and
+// swaps the buffers. The temp buffer is sized once, for full-word passes
+// and for min_bits-wide ones (the narrowest pass the caller will ask for).
+struct PermSort {
+  Ctx *c;
+  u64 n;
+  u32 *p, *p_out;
+  u64 *k, *k_out;
+  size_t tmp_bytes = 0;
+  void *tmp;
+  PermSort(Ctx *c_, u64 n_, int min_bits = 64) : c(c_), n(n_) {
+    auto &S = (*c->scr);
+    p = (u32 *)S.get(n * 4);
+    p_out = (u32 *)S.get(n * 4);
+    k = (u64 *)S.get(n * 8);
+    k_out = (u64 *)S.get(n * 8);
+    hipLaunchKernelGGL(k_iota, dim3(ngrid(n)), dim3(BLK), 0, c->stream, p, n);
+    for (int bits : {64, min_bits}) {
+      size_t nb = 0;
+      (void)rocprim::radix_sort_pairs(nullptr, nb, k, k_out, p, p_out,
+                                      (unsigned)n, 0, bits, c->stream);
+      tmp_bytes = std::max(tmp_bytes, nb);
+    }
+    tmp = S.get(tmp_bytes);
+  }
+  u64 *skey() const { return k; }
+  const u32 *perm() const { return p; }
+  void pass(int end_bit = 64) {
+    size_t nb = tmp_bytes;
+    (void)rocprim::radix_sort_pairs(tmp, nb, k, k_out, p, p_out, (unsigned)n,
+                                    0, end_bit, c->stream);
+    std::swap(p, p_out);
+  }
+};
 
 // Correction rows an apply kernel appends through *ocount.
 struct CorrBuf {
@@ -5243,6 +5286,165 @@ static const char *distinct_agg_error(const mz_gpu_aggregate &g,
   return nullptr;
 }
 
+// ---- snapshot-diff push protocol: the operators that keep
+// their groups' contents in an arrangement of their own (TopK, window
+// functions) and answer a push with f(new snapshot) - f(old snapshot) of
+// the changed groups.
+
+static int probe_impl(Ctx *ctx, mz_gpu_arr *lookup, const mz_gpu_updates *u,
+                      u32 stream_vb, int mode, int swap,
+                      const mz_gpu_closure *cl, int consolidate_out,
+                      mz_gpu_out **out);
+static DevBatch *arr_insert_dev(Ctx *ctx, mz_gpu_arr *a, DevUpdates d,
+                                u64 lower, u64 upper);
+
+// Pass-through closure: the probe reads each (key, val, net) of the probed
+// keys unchanged (the peek shape).
+static void pass_through_closure(u32 kw, u32 vb, mz_gpu_closure &cl) {
+  std::memset(&cl, 0, sizeof(cl));
+  cl.n_key_fields = 1;
+  cl.key_fields[0] = mz_gpu_field{MZ_SRC_KEY, 0, (u8)(8 * kw), 0, 0, 0, 0};
+  cl.n_val_fields = vb ? 1u : 0u;
+  if (vb)
+    cl.val_fields[0] =
+        mz_gpu_field{MZ_SRC_VAL_LOOKUP, 0, (u8)vb, 0, 0, 0, 0};
+  cl.out.key_words = kw;
+  cl.out.val_bytes = vb;
+}
+
+// One slice's correction rows: n rows in columns the operator allocated
+// with flat_alloc and the driver frees.
+struct SnapSeg {
+  FlatCols cols;
+  u64 n = 0;
+};
+
+// The push. The operator supplies
+//   eval(t, oldp, newp, &seg) -> bool: evaluate the two consolidated
+//     snapshots of one slice's changed groups (either may have no rows) into
+//     seg, old rows with sign -1 and new rows with +1, all at time t. Scratch
+//     is free for it. false stops the push; errors() must then say why.
+//   errors(total) -> nullptr or the message: called once, after everything
+//     queued has been synchronised, with the number of correction rows;
+//     total > max_rows was not consolidated and must be refused here.
+// A failed push leaves *out untouched and the slices installed so far
+// installed.
+template <class Eval, class Errors>
+static int snapshot_diff_push(mz_gpu_ctx *c, mz_gpu_arr *arr, u32 out_vb,
+                              u64 max_rows, const mz_gpu_updates *u,
+                              Eval &&eval, Errors &&errors,
+                              mz_gpu_out **out) {
+  Ctx *ctx = &c->impl;
+  (*ctx->scr).reset();
+  const u32 kw = arr->schema.kw, vb = arr->schema.vb;
+  DevUpdates d = stage_updates(ctx, u, kw, vb);
+  u64 n = d.n;
+  if (n == 0) {
+    *out = empty_out(ctx, kw, out_vb);
+    return 0;
+  }
+  // Owned sorted columns: they outlive spine merges' scratch resets.
+  FlatCols s = flat_alloc(ctx, n, kw, vb);
+  sort_gather(ctx, d.keys, kw, d.vals, vb, d.times, d.diffs, n, &s);
+  mz_gpu_closure cl;
+  pass_through_closure(kw, vb, cl);
+  std::vector<SnapSeg> segs;
+  u64 total = 0;
+  int rc = 0;
+  bool stopped = false;
+  for (auto [lo, hi, t] : time_slices(ctx, s.times, n, u->lower, u->upper)) {
+    u64 m = hi - lo;
+    Groups g = group_sorted(ctx, s.keys + lo * kw, kw, s.times + lo, m);
+    u64 G = *(u32 *)d2h_pinned(ctx, g.gid + (m - 1), 4);
+    // the probe delta: one row per changed group at time t
+    u64 *dg = dnew<u64>(ctx, G * kw);
+    u64 *gt = dnew<u64>(ctx, G);
+    i64 *gd = dnew<i64>(ctx, G);
+    hipLaunchKernelGGL(k_gather_group_keys, dim3(ngrid(G)), dim3(BLK), 0,
+                       ctx->stream, s.keys + lo * kw, kw, g.starts, g.gid, m,
+                       dg);
+    fill_u64(ctx, gt, G, t);
+    fill_u64(ctx, (u64 *)gd, G, 1);
+    mz_gpu_updates su{};
+    su.keys = dg;
+    su.vals = nullptr;
+    su.times = gt;
+    su.diffs = gd;
+    su.n = G;
+    su.lower = t;
+    su.upper = t + 1;
+    su.on_device = 1;
+    // snapshot the changed groups, install the slice, snapshot again
+    mz_gpu_out *oldp = nullptr, *newp = nullptr;
+    rc = probe_impl(ctx, arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &oldp);
+    if (!rc) {
+      DevUpdates sl{s.keys + lo * kw, s.vals + lo * vb, s.times + lo,
+                    s.diffs + lo, m};
+      arr_insert_dev(ctx, arr, sl, t, t + 1);
+      rc = probe_impl(ctx, arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &newp);
+    }
+    if (!rc) {
+      SnapSeg seg;
+      stopped = !eval(t, oldp, newp, &seg);
+      if (seg.cols.keys) {
+        segs.push_back(seg);
+        total += seg.n;
+      }
+    }
+    if (oldp) mz_gpu_out_release(c, oldp);
+    if (newp) mz_gpu_out_release(c, newp);
+    dfree(ctx, dg);
+    dfree(ctx, gt);
+    dfree(ctx, gd);
+    if (rc || stopped) break;
+  }
+  const char *why = nullptr;
+  if (!rc) {
+    // one slice (the steady state) is consolidated where it was emitted
+    const bool emitted = !stopped && total && total <= max_rows;
+    FlatCols all, o;
+    u64 Mc = 0;
+    if (emitted) {
+      all = segs[0].cols;
+      if (segs.size() > 1) {
+        all = flat_alloc(ctx, total, kw, out_vb);
+        u64 base = 0;
+        for (const SnapSeg &sg : segs) {
+          HIP_CHECK(hipMemcpyAsync(all.keys + base * kw, sg.cols.keys,
+                                   sg.n * kw * 8, hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+          if (out_vb)
+            HIP_CHECK(hipMemcpyAsync(all.vals + base * out_vb, sg.cols.vals,
+                                     sg.n * out_vb, hipMemcpyDeviceToDevice,
+                                     ctx->stream));
+          HIP_CHECK(hipMemcpyAsync(all.times + base, sg.cols.times, sg.n * 8,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+          HIP_CHECK(hipMemcpyAsync(all.diffs + base, sg.cols.diffs, sg.n * 8,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+          base += sg.n;
+        }
+      }
+      DevUpdates pin{all.keys, all.vals, all.times, all.diffs, total};
+      o = consolidate_dev(ctx, kw, out_vb, pin, &Mc);
+    }
+    why = errors(total);
+    if (emitted && segs.size() > 1) flat_free(ctx, all);
+    if (why)
+      flat_free(ctx, o);
+    else
+      *out = emitted ? make_out(o, Mc, kw, out_vb)
+                     : empty_out(ctx, kw, out_vb);
+  }
+  for (SnapSeg &sg : segs) flat_free(ctx, sg.cols);
+  flat_free(ctx, s);
+  if (rc) return rc;
+  if (why) {
+    ctx->err = why;
+    return -1;
+  }
+  return 0;
+}
+
 extern "C" {
 
 mz_gpu_ctx *mz_gpu_init(const mz_gpu_cfg *cfg) {
@@ -6039,16 +6241,8 @@ int mz_gpu_peek(mz_gpu_ctx *c, mz_gpu_arr *arr, const uint64_t *keys,
   u.lower = time;
   u.upper = time + 1;
   u.on_device = 0;
-  mz_gpu_closure cl{};
-  cl.n_filters = 0;
-  cl.n_key_fields = 1;
-  cl.key_fields[0] = mz_gpu_field{MZ_SRC_KEY, 0, (u8)(8 * kw), 0, 0, 0, 0};
-  cl.n_val_fields = vb ? 1u : 0u;
-  if (vb)
-    cl.val_fields[0] =
-        mz_gpu_field{MZ_SRC_VAL_LOOKUP, 0, (u8)vb, 0, 0, 0, 0};
-  cl.out.key_words = kw;
-  cl.out.val_bytes = vb;
+  mz_gpu_closure cl;
+  pass_through_closure(kw, vb, cl);
   return probe_impl(&c->impl, arr, &u, 0, PM_HALF_LE, 0, &cl, 1, out);
 }
 
@@ -6300,27 +6494,12 @@ static std::string peek_finish(Ctx *ctx, const mz_gpu_finishing *fin, u32 kw,
   const u32 *perm = nullptr;
   const i64 *cnt = o.diffs;
   if (fin->n_order) {
-    u32 *p = (u32 *)S.get(n * 4), *p_out = (u32 *)S.get(n * 4);
-    u64 *skey = (u64 *)S.get(n * 8), *skey_out = (u64 *)S.get(n * 8);
-    hipLaunchKernelGGL(k_iota, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream, p,
-                       n);
-    size_t tmp_bytes = 0, tmp_bytes1 = 0;  // full-word and NULL-rank passes
-    (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes, skey, skey_out, p,
-                                    p_out, (unsigned)n, 0, 64, ctx->stream);
-    (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes1, skey, skey_out, p,
-                                    p_out, (unsigned)n, 0, 1, ctx->stream);
-    tmp_bytes = std::max(tmp_bytes, tmp_bytes1);
-    void *tmp = S.get(tmp_bytes);
+    PermSort ps(ctx, n, 1);  // full-word and 1-bit NULL-rank passes
     auto pass = [&](const mz_gpu_peek_order &oc, u32 part) {
       hipLaunchKernelGGL(k_peek_sortkey, dim3(ngrid(n)), dim3(BLK), 0,
-                         ctx->stream, o.keys, kw, o.vals, vb, p, skey, n, oc,
-                         part);
-      size_t nb = tmp_bytes;
-      (void)rocprim::radix_sort_pairs(tmp, nb, skey, skey_out, p, p_out,
-                                      (unsigned)n, 0,
-                                      part == PEEK_KEY_NULL ? 1 : 64,
-                                      ctx->stream);
-      std::swap(p, p_out);
+                         ctx->stream, o.keys, kw, o.vals, vb, ps.perm(),
+                         ps.skey(), n, oc, part);
+      ps.pass(part == PEEK_KEY_NULL ? 1 : 64);
     };
     for (int j = (int)fin->n_order - 1; j >= 0; j--) {
       const mz_gpu_peek_order &oc = fin->order[j];
@@ -6330,8 +6509,8 @@ static std::string peek_finish(Ctx *ctx, const mz_gpu_finishing *fin, u32 kw,
     }
     i64 *sd = (i64 *)S.get(n * 8);
     hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0,
-                       ctx->stream, o.diffs, p, sd, n);
-    perm = p;
+                       ctx->stream, o.diffs, ps.perm(), sd, n);
+    perm = ps.perm();
     cnt = sd;
   }
   u64 *pre = (u64 *)S.get(n * 8);
@@ -7136,20 +7315,6 @@ int mz_gpu_threshold_push(mz_gpu_ctx *c, mz_gpu_thr *op,
   return 0;
 }
 
-// Pass-through closure: the group-eval probe reads each (key, val, net)
-// of the probed groups unchanged (the peek shape).
-static void topk_pass_cl(u32 kw, u32 vb, mz_gpu_closure &cl) {
-  std::memset(&cl, 0, sizeof(cl));
-  cl.n_key_fields = 1;
-  cl.key_fields[0] = mz_gpu_field{MZ_SRC_KEY, 0, (u8)(8 * kw), 0, 0, 0, 0};
-  cl.n_val_fields = vb ? 1u : 0u;
-  if (vb)
-    cl.val_fields[0] =
-        mz_gpu_field{MZ_SRC_VAL_LOOKUP, 0, (u8)vb, 0, 0, 0, 0};
-  cl.out.key_words = kw;
-  cl.out.val_bytes = vb;
-}
-
 // One eval set (a consolidated (key,val,net) snapshot of the changed
 // groups, pe->n >= 1 rows) ordered by (group, order columns, canonical val
 // tie-break), in scratch: the ordered columns, the key groups and the
@@ -7171,35 +7336,21 @@ static OrderedSnap order_snapshot(Ctx *ctx, u32 kw, u32 vb, u32 n_order,
   const u64 *keys = (const u64 *)pe->keys;
   const u8 *vals = (const u8 *)pe->vals;
   const i64 *diffs = (const i64 *)pe->diffs;
-  u32 *perm = (u32 *)S.get(n * 4);
-  u32 *perm_out = (u32 *)S.get(n * 4);
-  u64 *skey = (u64 *)S.get(n * 8);
-  u64 *skey_out = (u64 *)S.get(n * 8);
-  hipLaunchKernelGGL(k_iota, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     perm, n);
-  size_t tmp_bytes = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, tmp_bytes, skey, skey_out, perm,
-                                  perm_out, (unsigned)n, 0, 64, ctx->stream);
-  void *tmp = S.get(tmp_bytes);
-  auto radix_pass = [&]() {
-    size_t nb = tmp_bytes;
-    (void)rocprim::radix_sort_pairs(tmp, nb, skey, skey_out, perm, perm_out,
-                                    (unsigned)n, 0, 64, ctx->stream);
-    std::swap(perm, perm_out);
-  };
+  PermSort ps(ctx, n);
   for (int j = (int)n_order - 1; j >= 0; j--) {
     const mz_gpu_order_col &oc = order[j];
     hipLaunchKernelGGL(k_order_sortkey, dim3(ngrid(n)), dim3(BLK), 0,
-                       ctx->stream, vals, vb, perm, skey, n, (u32)oc.off,
-                       (u32)oc.width, (u32)oc.desc);
-    radix_pass();
+                       ctx->stream, vals, vb, ps.perm(), ps.skey(), n,
+                       (u32)oc.off, (u32)oc.width, (u32)oc.desc);
+    ps.pass();
   }
   for (int w = (int)kw - 1; w >= 0; w--) {
     hipLaunchKernelGGL(k_sortkey_key, dim3(ngrid(n)), dim3(BLK), 0,
-                       ctx->stream, keys, kw, (u32)w, perm, skey, n,
+                       ctx->stream, keys, kw, (u32)w, ps.perm(), ps.skey(), n,
                        (u64)0, (u32 *)nullptr);
-    radix_pass();
+    ps.pass();
   }
+  const u32 *perm = ps.perm();
   u64 *sk2 = (u64 *)S.get(n * kw * 8);
   u8 *sv2 = (u8 *)S.get(std::max<u64>(n * vb, 1));
   i64 *sd2 = (i64 *)S.get(n * 8);
@@ -7220,8 +7371,8 @@ static OrderedSnap order_snapshot(Ctx *ctx, u32 kw, u32 vb, u32 n_order,
 // Order one eval set, compute each row's kept multiplicity window and
 // append corrections with the given sign.
 static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
-                           u64 t, i64 sign, u64 *pk, u8 *pv, u64 *pt,
-                           i64 *pd, unsigned long long *ocount) {
+                           u64 t, i64 sign, const FlatCols &p,
+                           unsigned long long *ocount) {
   u64 n = pe->n;
   if (!n) return;
   u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
@@ -7232,7 +7383,7 @@ static void topk_eval_emit(Ctx *ctx, mz_gpu_topk *op, mz_gpu_out *pe,
   hipLaunchKernelGGL(k_topk_kept, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
                      s.keys, kw, s.vals, vb, s.diffs, s.pre, s.g.starts,
                      s.g.gid, n, op->spec.offset, (i64)op->spec.limit, t,
-                     sign, pk, pv, pt, pd, ocount);
+                     sign, p.keys, p.vals, p.times, p.diffs, ocount);
 }
 
 mz_gpu_topk *mz_gpu_topk_create(mz_gpu_ctx *c, const mz_gpu_topk_spec *spec) {
@@ -7254,147 +7405,32 @@ void mz_gpu_topk_drop(mz_gpu_ctx *c, mz_gpu_topk *op) {
 int mz_gpu_topk_push(mz_gpu_ctx *c, mz_gpu_topk *op,
                      const mz_gpu_updates *u, mz_gpu_out **out) {
   Ctx *ctx = &c->impl;
-  (*ctx->scr).reset();
-  u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
-  DevUpdates d = stage_updates(ctx, u, kw, vb);
-  u64 n = d.n;
-  if (n == 0) {
-    *out = empty_out(ctx, kw, vb);
-    return 0;
-  }
-  // Owned sorted columns: they outlive spine merges' scratch resets.
-  u32 *perm = dnew<u32>(ctx, n);
-  sort_updates(ctx, d.keys, kw, d.vals, vb, d.times, n, perm, true);
-  u64 *sk = dnew<u64>(ctx, n * kw);
-  u8 *sv = (u8 *)dmalloc(ctx, std::max<u64>(n * vb, 1));
-  u64 *stm = dnew<u64>(ctx, n);
-  i64 *sd = dnew<i64>(ctx, n);
-  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
-                     ctx->stream, d.keys, kw, perm, sk, n);
-  if (vb)
-    hipLaunchKernelGGL(k_gather_valrows, dim3(ngrid(n)), dim3(BLK), 0,
-                       ctx->stream, d.vals, vb, perm, sv, n);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.times, perm, stm, n);
-  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.diffs, perm, sd, n);
-  std::vector<TimeSlice> slices =
-      time_slices(ctx, stm, n, u->lower, u->upper);
-  std::vector<std::array<void *, 4>> segs;
-  std::vector<u64> segn;
-  int rc = 0;
-  for (auto [lo, hi, t] : slices) {
-    u64 m = hi - lo;
-    auto &S = (*ctx->scr);
-    Groups g = group_sorted(ctx, sk + lo * kw, kw, stm + lo, m);
-    u32 G32 = 0;
-    HIP_CHECK(hipMemcpyAsync(&G32, g.gid + (m - 1), 4, hipMemcpyDeviceToHost,
-                             ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    u64 G = G32;
-    u64 *dg = dnew<u64>(ctx, G * kw);
-    u64 *gt = dnew<u64>(ctx, G);
-    i64 *gd = dnew<i64>(ctx, G);
-    hipLaunchKernelGGL(k_gather_group_keys, dim3(ngrid(G)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, g.starts, g.gid, m,
-                       dg);
-    hipLaunchKernelGGL(k_fill_u64, dim3(ngrid(G)), dim3(BLK), 0,
-                       ctx->stream, gt, G, t);
-    hipLaunchKernelGGL(k_fill_i64, dim3(ngrid(G)), dim3(BLK), 0,
-                       ctx->stream, gd, G, (i64)1);
-    mz_gpu_updates su{};
-    su.keys = dg;
-    su.vals = nullptr;
-    su.times = gt;
-    su.diffs = gd;
-    su.n = G;
-    su.lower = t;
-    su.upper = t + 1;
-    su.on_device = 1;
-    mz_gpu_closure cl;
-    topk_pass_cl(kw, vb, cl);
-    mz_gpu_out *oldp = nullptr, *newp = nullptr;
-    rc = probe_impl(ctx, op->arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &oldp);
-    if (rc) break;
-    DevUpdates sl{sk + lo * kw, vb ? sv + lo * vb : sv, stm + lo, sd + lo,
-                  m};
-    arr_insert_dev(ctx, op->arr, sl, t, t + 1);
-    rc = probe_impl(ctx, op->arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &newp);
-    if (rc) break;
+  const u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
+  // each snapshot row emits at most one correction, appended through
+  // *ocount into a zero-filled segment: the unused rows consolidate away
+  auto eval = [&](u64 t, mz_gpu_out *oldp, mz_gpu_out *newp, SnapSeg *seg) {
     u64 capn = oldp->n + newp->n;
-    if (capn) {
-      u64 *pk = dnew<u64>(ctx, capn * kw);
-      u8 *pv = (u8 *)dmalloc(ctx, std::max<u64>(capn * vb, 1));
-      u64 *pt = dnew<u64>(ctx, capn);
-      i64 *pd = dnew<i64>(ctx, capn);
-      fill_u64(ctx, pk, capn * kw, 0);
-      fill_u8(ctx, pv, std::max<u64>(capn * vb, 1), 0);
-      fill_u64(ctx, pt, capn, 0);
-      fill_u64(ctx, (u64 *)pd, capn, 0);
-      unsigned long long *ocount = (unsigned long long *)S.get(8);
-      fill_u64(ctx, (u64 *)ocount, 1, 0);
-      topk_eval_emit(ctx, op, oldp, t, -1, pk, pv, pt, pd, ocount);
-      topk_eval_emit(ctx, op, newp, t, +1, pk, pv, pt, pd, ocount);
-      segs.push_back({pk, pv, pt, pd});
-      segn.push_back(capn);
-    }
-    mz_gpu_out_release(c, oldp);
-    mz_gpu_out_release(c, newp);
-    dfree(ctx, dg);
-    dfree(ctx, gt);
-    dfree(ctx, gd);
-  }
-  u64 total = 0;
-  for (u64 x : segn) total += x;
-  u64 errflag = 0;
-  if (!rc) {
-    if (total == 0) {
-      HIP_CHECK(hipMemcpyAsync(&errflag, op->d_err, 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (!errflag) *out = empty_out(ctx, kw, vb);
-    } else {
-      u64 *ck2 = dnew<u64>(ctx, total * kw);
-      u8 *cv2 = (u8 *)dmalloc(ctx, std::max<u64>(total * vb, 1));
-      u64 *ct2 = dnew<u64>(ctx, total);
-      i64 *cd2 = dnew<i64>(ctx, total);
-      u64 base = 0;
-      for (size_t i = 0; i < segs.size(); i++) {
-        u64 m2 = segn[i];
-        HIP_CHECK(hipMemcpyAsync(ck2 + base * kw, segs[i][0],
-                                 m2 * kw * 8, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-        if (vb)
-          HIP_CHECK(hipMemcpyAsync(cv2 + base * vb, segs[i][1], m2 * vb,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(ct2 + base, segs[i][2], m2 * 8,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(cd2 + base, segs[i][3], m2 * 8,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-        base += m2;
-      }
-      DevUpdates pin{ck2, cv2, ct2, cd2, total};
-      u64 Mc;
-      FlatCols o = consolidate_dev(ctx, kw, vb, pin, &Mc);
-      HIP_CHECK(hipMemcpyAsync(&errflag, op->d_err, 8,
-                               hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      for (void *p : {(void *)ck2, (void *)cv2, (void *)ct2, (void *)cd2})
-        dfree(ctx, p);
-      if (!errflag) *out = make_out(o, Mc, kw, vb);
-    }
-  }
-  for (auto &sg : segs)
-    for (void *p : sg) dfree(ctx, p);
-  for (void *p : {(void *)perm, (void *)sk, (void *)sv, (void *)stm,
-                  (void *)sd})
-    dfree(ctx, p);
-  if (rc) return rc;
-  if (errflag) {
-    ctx->err = "negative multiplicities in TopK";
-    return -1;
-  }
-  return 0;
+    if (!capn) return true;
+    seg->cols = flat_alloc(ctx, capn, kw, vb);
+    seg->n = capn;
+    const FlatCols &p = seg->cols;
+    fill_u64(ctx, p.keys, capn * kw, 0);
+    fill_u8(ctx, p.vals, std::max<u64>(capn * vb, 1), 0);
+    fill_u64(ctx, p.times, capn, 0);
+    fill_u64(ctx, (u64 *)p.diffs, capn, 0);
+    unsigned long long *ocount =
+        (unsigned long long *)(*ctx->scr).get(8);
+    fill_u64(ctx, (u64 *)ocount, 1, 0);
+    topk_eval_emit(ctx, op, oldp, t, -1, p, ocount);
+    topk_eval_emit(ctx, op, newp, t, +1, p, ocount);
+    return true;
+  };
+  auto errors = [&](u64) -> const char * {
+    return *(const u64 *)d2h_pinned(ctx, op->d_err, 8)
+               ? "negative multiplicities in TopK"
+               : nullptr;
+  };
+  return snapshot_diff_push(c, op->arr, vb, UINT64_MAX, u, eval, errors, out);
 }
 
 // ------------------------------------------------------ window functions
@@ -7428,9 +7464,6 @@ void mz_gpu_window_drop(mz_gpu_ctx *c, mz_gpu_window *op) {
   delete op;
 }
 
-// Order one eval set of pe->n >= 1 rows as TopK does and derive what the
-// emit kernel reads: peer head flags, their max-scan (peer-start rows) and
-// their sum-scan (dense ranks). All in scratch.
 // The aggregates' prefix structures over one ordered snapshot, in scratch:
 // per SUM datum the wrapping 128-bit prefix of m x, per nullable datum the
 // prefix of m [non-NULL], per MIN / MAX the extremum scanned by partition
@@ -7522,6 +7555,9 @@ static WinAggs window_agg_prefixes(Ctx *ctx, const mz_gpu_window_spec &sp,
   return A;
 }
 
+// Order one eval set of pe->n >= 1 rows as TopK does and derive what the
+// emit kernel reads: peer head flags, their max-scan (peer-start rows) and
+// their sum-scan (dense ranks). All in scratch.
 static WinSnap window_eval(Ctx *ctx, mz_gpu_window *op, mz_gpu_out *pe,
                            WinAggs *aggs) {
   u64 n = pe->n;
@@ -7555,191 +7591,77 @@ static WinSnap window_eval(Ctx *ctx, mz_gpu_window *op, mz_gpu_out *pe,
 int mz_gpu_window_push(mz_gpu_ctx *c, mz_gpu_window *op,
                        const mz_gpu_updates *u, mz_gpu_out **out) {
   Ctx *ctx = &c->impl;
-  (*ctx->scr).reset();
   const u32 kw = op->spec.in.key_words, vb = op->spec.in.val_bytes;
   const u32 ovb = op->spec.out.val_bytes;
-  const u64 kMaxExpanded = 0x7FFFFFFFull;
-  DevUpdates d = stage_updates(ctx, u, kw, vb);
-  u64 n = d.n;
-  if (n == 0) {
-    *out = empty_out(ctx, kw, ovb);
-    return 0;
-  }
-  // Owned sorted columns: they outlive spine merges' scratch resets.
-  u32 *perm = dnew<u32>(ctx, n);
-  sort_updates(ctx, d.keys, kw, d.vals, vb, d.times, n, perm, true);
-  u64 *sk = dnew<u64>(ctx, n * kw);
-  u8 *sv = (u8 *)dmalloc(ctx, std::max<u64>(n * vb, 1));
-  u64 *stm = dnew<u64>(ctx, n);
-  i64 *sd = dnew<i64>(ctx, n);
-  hipLaunchKernelGGL(k_gather_keyrows, dim3(ngrid(n)), dim3(BLK), 0,
-                     ctx->stream, d.keys, kw, perm, sk, n);
-  if (vb)
-    hipLaunchKernelGGL(k_gather_valrows, dim3(ngrid(n)), dim3(BLK), 0,
-                       ctx->stream, d.vals, vb, perm, sv, n);
-  hipLaunchKernelGGL(k_gather_u64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.times, perm, stm, n);
-  hipLaunchKernelGGL(k_gather_i64, dim3(ngrid(n)), dim3(BLK), 0, ctx->stream,
-                     d.diffs, perm, sd, n);
-  std::vector<TimeSlice> slices =
-      time_slices(ctx, stm, n, u->lower, u->upper);
+  const u64 kMaxExpanded = 0x7FFFFFFFull, kMaxTotal = 0xFFFFFFFFull;
   WinFuncs F;
   F.n = op->spec.n_funcs;
   for (u32 f = 0; f < MZ_GPU_MAX_WFUNCS; f++) F.f[f] = op->spec.funcs[f];
-  std::vector<FlatCols> segs;
-  std::vector<u64> segn;
-  u64 total = 0;
-  int rc = 0;
   bool negative = false, too_big = false, sum_range = false;
+  auto eval = [&](u64 t, mz_gpu_out *oldp, mz_gpu_out *newp, SnapSeg *seg) {
+    WinSnap so{}, sn{};
+    WinAggs ao{}, an{};
+    if (oldp->n) so = window_eval(ctx, op, oldp, &ao);
+    if (newp->n) sn = window_eval(ctx, op, newp, &an);
+    u64 mo = oldp->n, mn = newp->n;  // output rows of each snapshot
+    if (op->expand) {
+      // the expanded sizes are read back before anything of that size is
+      // allocated, with the error words that say whether they mean
+      // anything
+      u64 *stage = (u64 *)ctx->pin;
+      stage[0] = stage[1] = 0;
+      if (so.n)
+        HIP_CHECK(hipMemcpyAsync(stage, so.pre + (so.n - 1), 8,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      if (sn.n)
+        HIP_CHECK(hipMemcpyAsync(stage + 1, sn.pre + (sn.n - 1), 8,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(stage + 2, op->d_err, 16,
+                               hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      mo = stage[0];
+      mn = stage[1];
+      negative = stage[2] != 0;
+      too_big = stage[3] != 0 || mo > kMaxExpanded || mn > kMaxExpanded;
+    }
+    if (negative || too_big) return false;
+    if (!(mo + mn)) return true;
+    seg->cols = flat_alloc(ctx, mo + mn, kw, ovb);
+    seg->n = mo + mn;
+    const FlatCols &p = seg->cols;
+    auto emit = op->has_agg ? k_window_emit<true> : k_window_emit<false>;
+    if (mo)
+      hipLaunchKernelGGL(emit, dim3(ngrid(mo)), dim3(BLK), 0, ctx->stream, so,
+                         F, ao, kw, vb, ovb, op->expand ? 1 : 0, mo, (u64)0,
+                         t, (i64)-1, p.keys, p.vals, p.times, p.diffs,
+                         op->d_err);
+    if (mn)
+      hipLaunchKernelGGL(emit, dim3(ngrid(mn)), dim3(BLK), 0, ctx->stream, sn,
+                         F, an, kw, vb, ovb, op->expand ? 1 : 0, mn, mo, t,
+                         (i64)1, p.keys, p.vals, p.times, p.diffs, op->d_err);
+    return true;
+  };
   // the error words once everything queued has run: a spec holding SUM
   // needs [1] without expansion too, and [2] is the emit kernels' own
-  auto read_errs = [&]() {
-    const u64 *e = (const u64 *)d2h_pinned(ctx, op->d_err, 24);
-    negative = e[0] != 0;
-    if (op->has_sum) {
-      too_big = too_big || e[1] != 0;
-      sum_range = e[2] != 0;
-    }
-  };
-  for (auto [lo, hi, t] : slices) {
-    u64 m = hi - lo;
-    Groups g = group_sorted(ctx, sk + lo * kw, kw, stm + lo, m);
-    u64 G = *(u32 *)d2h_pinned(ctx, g.gid + (m - 1), 4);
-    u64 *dg = dnew<u64>(ctx, G * kw);
-    u64 *gt = dnew<u64>(ctx, G);
-    i64 *gd = dnew<i64>(ctx, G);
-    hipLaunchKernelGGL(k_gather_group_keys, dim3(ngrid(G)), dim3(BLK), 0,
-                       ctx->stream, sk + lo * kw, kw, g.starts, g.gid, m,
-                       dg);
-    fill_u64(ctx, gt, G, t);
-    fill_u64(ctx, (u64 *)gd, G, 1);
-    mz_gpu_updates su{};
-    su.keys = dg;
-    su.vals = nullptr;
-    su.times = gt;
-    su.diffs = gd;
-    su.n = G;
-    su.lower = t;
-    su.upper = t + 1;
-    su.on_device = 1;
-    mz_gpu_closure cl;
-    topk_pass_cl(kw, vb, cl);
-    // snapshot the changed partitions, install the slice, snapshot again
-    mz_gpu_out *oldp = nullptr, *newp = nullptr;
-    rc = probe_impl(ctx, op->arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &oldp);
-    if (!rc) {
-      DevUpdates sl{sk + lo * kw, vb ? sv + lo * vb : sv, stm + lo, sd + lo,
-                    m};
-      arr_insert_dev(ctx, op->arr, sl, t, t + 1);
-      rc = probe_impl(ctx, op->arr, &su, 0, PM_HALF_LE, 0, &cl, 1, &newp);
-    }
-    if (!rc) {
-      WinSnap so{}, sn{};
-      WinAggs ao{}, an{};
-      if (oldp->n) so = window_eval(ctx, op, oldp, &ao);
-      if (newp->n) sn = window_eval(ctx, op, newp, &an);
-      u64 mo = oldp->n, mn = newp->n;  // output rows of each snapshot
-      if (op->expand) {
-        // the expanded sizes are read back before anything of that size is
-        // allocated, with the error words that say whether they mean
-        // anything
-        u64 *stage = (u64 *)ctx->pin;
-        stage[0] = stage[1] = 0;
-        if (so.n)
-          HIP_CHECK(hipMemcpyAsync(stage, so.pre + (so.n - 1), 8,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        if (sn.n)
-          HIP_CHECK(hipMemcpyAsync(stage + 1, sn.pre + (sn.n - 1), 8,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(stage + 2, op->d_err, 16,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        mo = stage[0];
-        mn = stage[1];
-        negative = stage[2] != 0;
-        too_big = stage[3] != 0 || mo > kMaxExpanded || mn > kMaxExpanded;
-      }
-      if (!negative && !too_big && mo + mn) {
-        FlatCols seg = flat_alloc(ctx, mo + mn, kw, ovb);
-        auto emit = op->has_agg ? k_window_emit<true> : k_window_emit<false>;
-        if (mo)
-          hipLaunchKernelGGL(emit, dim3(ngrid(mo)), dim3(BLK), 0,
-                             ctx->stream, so, F, ao, kw, vb, ovb,
-                             op->expand ? 1 : 0, mo, (u64)0, t, (i64)-1,
-                             seg.keys, seg.vals, seg.times, seg.diffs,
-                             op->d_err);
-        if (mn)
-          hipLaunchKernelGGL(emit, dim3(ngrid(mn)), dim3(BLK), 0,
-                             ctx->stream, sn, F, an, kw, vb, ovb,
-                             op->expand ? 1 : 0, mn, mo, t, (i64)1, seg.keys,
-                             seg.vals, seg.times, seg.diffs, op->d_err);
-        segs.push_back(seg);
-        segn.push_back(mo + mn);
-        total += mo + mn;
-      }
-    }
-    if (oldp) mz_gpu_out_release(c, oldp);
-    if (newp) mz_gpu_out_release(c, newp);
-    dfree(ctx, dg);
-    dfree(ctx, gt);
-    dfree(ctx, gd);
-    if (rc || negative || too_big) break;
-  }
-  if (!rc && !negative && !too_big && total > 0xFFFFFFFFull) too_big = true;
-  if (!rc && !negative && !too_big) {
-    if (total == 0) {
-      read_errs();
-      if (!negative && !too_big && !sum_range) *out = empty_out(ctx, kw, ovb);
-    } else {
-      // one slice (the steady state) is consolidated where it was emitted
-      FlatCols all = segs[0];
-      if (segs.size() > 1) {
-        all = flat_alloc(ctx, total, kw, ovb);
-        u64 base = 0;
-        for (size_t i = 0; i < segs.size(); i++) {
-          u64 m2 = segn[i];
-          HIP_CHECK(hipMemcpyAsync(all.keys + base * kw, segs[i].keys,
-                                   m2 * kw * 8, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-          HIP_CHECK(hipMemcpyAsync(all.vals + base * ovb, segs[i].vals,
-                                   m2 * ovb, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-          HIP_CHECK(hipMemcpyAsync(all.times + base, segs[i].times, m2 * 8,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-          HIP_CHECK(hipMemcpyAsync(all.diffs + base, segs[i].diffs, m2 * 8,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-          base += m2;
+  auto errors = [&](u64 total) -> const char * {
+    if (!negative && !too_big) {
+      if (total > kMaxTotal) {
+        too_big = true;
+      } else {
+        const u64 *e = (const u64 *)d2h_pinned(ctx, op->d_err, 24);
+        negative = e[0] != 0;
+        if (op->has_sum) {
+          too_big = e[1] != 0;
+          sum_range = e[2] != 0;
         }
       }
-      DevUpdates pin{all.keys, all.vals, all.times, all.diffs, total};
-      u64 Mc;
-      FlatCols o = consolidate_dev(ctx, kw, ovb, pin, &Mc);
-      read_errs();
-      if (segs.size() > 1) flat_free(ctx, all);
-      if (negative || too_big || sum_range)
-        flat_free(ctx, o);
-      else
-        *out = make_out(o, Mc, kw, ovb);
     }
-  }
-  for (FlatCols &sg : segs) flat_free(ctx, sg);
-  for (void *p : {(void *)perm, (void *)sk, (void *)sv, (void *)stm,
-                  (void *)sd})
-    dfree(ctx, p);
-  if (rc) return rc;
-  if (negative) {
-    ctx->err = "negative multiplicities in window";
-    return -1;
-  }
-  if (too_big) {
-    ctx->err = "window: expanded partition exceeds 2^31 rows";
-    return -1;
-  }
-  if (sum_range) {
-    ctx->err = "window: SUM out of int64 range";
-    return -1;
-  }
-  return 0;
+    if (negative) return "negative multiplicities in window";
+    if (too_big) return "window: expanded partition exceeds 2^31 rows";
+    if (sum_range) return "window: SUM out of int64 range";
+    return nullptr;
+  };
+  return snapshot_diff_push(c, op->arr, ovb, kMaxTotal, u, eval, errors, out);
 }
 
 int mz_gpu_partition(mz_gpu_ctx *c, const mz_gpu_schema *s,
@@ -8086,6 +8008,7 @@ static int minmax_push_dev_impl(Ctx *ctx, mz_gpu_minmax *op, DevUpdates d0,
     u32 *misspos = (u32 *)S.get((G + 1) * 4);
     u64 Mn = exclusive_scan_u32(ctx, miss, misspos, G);
     if (T.n_rows + Mn > T.st.capacity) {
+      for (void *p : owned) dfree(ctx, p);
       ctx->err = "minmax state capacity exceeded";
       return -1;
     }
